@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py — fwd+bwd frames/s of the dn-splatter rendering hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c1] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c1] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...);
+with --dump-outputs it also writes what the last timed step computed (dump_outputs).  Everything else below — the
+per-stage and roofline figures, the eager drop-in figure, the index-exact section, the other workloads, the multi-GPU
+accounting and the CPU baseline — is measured only with --full.
 
 One step = one pass of the hot path over one camera per GPU: ``get_outputs`` of the host mirror of
 ``DNSplatterModel.get_outputs`` (dn_splatter/dn_model.py:404-612 — activations, projection, SH, per-Gaussian
@@ -12,7 +17,7 @@ backward from dense random cotangents on rgb/depth/normal/accumulation to the si
 N > 1, the RCCL all-reduce (mean) of those gradients — 236 B per Gaussian in one flat bucket.  Inputs are
 synthetic random-init Gaussians (the reference's own initialisation) already resident in HBM.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0; with --full it carries these extra objects:
   roofline      — the dominant stage's algorithmic HBM bytes per launch / its mean HIP-event duration in the
                   timed region, against the 8 TB/s HBM3E peak (guides/MI355X_MICROARCH.md).  Only that stage is
                   bracketed with events inside the timed region (an event pair costs a ~6 us bubble on the stream);
@@ -81,6 +86,41 @@ FIRST_TOUCH_STEPS = 2
 PREROLL_STEPS = 12
 SH_K = 16
 D_CH = 7
+# --dump-outputs: a fixed sample of pixels and of Gaussian rows (all of them when there are fewer), the same in every run of a
+# workload, so that two builds can be compared output for output.  At C2 / C5: 8 MiB of images + 30 MiB of gradients.
+DUMP_PIXELS = 1 << 18
+DUMP_ROWS = 1 << 17
+DUMP_SEED = 12345
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, images, grads, loss=None):
+    """Writes what one step handed its caller — the images of ``get_outputs`` (``images``: name -> [H, W, C]), the loss if the
+    step computed one, the gradients of the optimised tensors (``grads``: name -> [N, ...]) — as ``out_dir/<name>.npy`` in
+    float32: every image at the same DUMP_PIXELS sampled pixels ([n, C]), every gradient at the same DUMP_ROWS sampled
+    Gaussians ([n, ...] in row order)."""
+    import numpy as np
+
+    def sample(count, n):
+        if count <= n:
+            return torch.arange(count)
+        return torch.randperm(count, generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+
+    arrays = {}
+    for name, t in images.items():
+        flat = t.detach().reshape(-1, t.shape[-1])
+        arrays[name] = flat[sample(flat.shape[0], DUMP_PIXELS).to(flat.device)]
+    if loss is not None:
+        arrays["loss"] = loss.detach().reshape(1)
+    for name, g in grads.items():
+        arrays["grad_" + name] = g.detach()[sample(g.shape[0], DUMP_ROWS).to(g.device)]
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def _strip_comments(src: str) -> str:
@@ -493,12 +533,12 @@ def child_workload(workload, losses, steps, scene=None, extra_args=()):
     """Another BASELINE workload measured by THIS script in a process of its own (same method as the headline: graph replay,
     pre-roll, device stamps around the dominant stage, counting step), started after the headline's timed region; returns the
     fields of its JSON line that BASELINE.md section 2 asks for.  A process of its own, because a second and third HIP-graph
-    capture with other buffer sizes inside one process crashed the HIP runtime in hipStreamEndCapture on ROCm 7.2 (round 4,
-    gpurun_out/r04b) and a crash there must not take the headline line with it."""
+    capture with other buffer sizes inside one process crashed the HIP runtime in hipStreamEndCapture on ROCm 7.2 (round 4)
+    and a crash there must not take the headline line with it."""
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(steps), "--warmup", "3",
-           "--no-cpu-baseline", "--no-strict", "--no-extra-workloads"] + (["--losses", losses] if losses else [])
+           "--full", "--no-cpu-baseline", "--no-strict", "--no-extra-workloads"] + (["--losses", losses] if losses else [])
     if scene:
         cmd += ["--scene", scene]
     cmd += list(extra_args)
@@ -533,8 +573,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-crop", type=int, default=None, help="time the CPU baseline on a centre crop of this size instead of a full frame")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-crop", type=int, default=None, help="--full: time the CPU baseline on a centre crop of this size instead of a full frame")
     ap.add_argument("--bin-policy", default="deferred", choices=["sync", "capacity", "deferred"],
                     help="how the host learns the frame's intersection count (dn-splatter_amd/_ops.py BIN_POLICY): 'deferred' never "
                          "waits for it in the steady state (verified as soon as it has arrived, an overflow raises)")
@@ -573,18 +613,28 @@ def main():
     ap.add_argument("--lean", action="store_true",
                     help="profiling runs (rocprofv3 --kernel-trace / --pmc serialise every launch): eager launches, no pre-roll, no "
                          "counting step, no strict-index-parity section")
-    ap.add_argument("--no-strict", action="store_true", help="skip the index-exact (gsplat tile boxes) section after the timed region")
+    ap.add_argument("--no-strict", action="store_true", help="--full: skip the index-exact (gsplat tile boxes) section after the timed region")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="skip the short C3 / C5 / C5-with-fused-losses sections a default C2 run appends (extra_workloads in the JSON line)")
+                    help="--full: skip the short C3 / C5 / C5-with-fused-losses sections a C2 run appends (extra_workloads in the JSON line)")
     ap.add_argument("--scene", default="reference_init", choices=["reference_init", "anisotropic", "morton"],
                     help="reference_init: the reference's random initialisation (BASELINE.md); anisotropic: the parity suite's "
                          "anisotropic / spread-opacity scene at the workload's size (make_scene)")
     ap.add_argument("--section", default=None, choices=["train_loop"],
-                    help="run one of the side sections a default C2 run starts as child processes, print its JSON line(s) and exit")
+                    help="run one of the side sections a --full C2 run starts as child processes, print its JSON line(s) and exit")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, count them with one all-reduce and print {n_gpus, ranks_seen} without rendering (works "
                          "without a GPU over gloo: the CPU test of the --gpus N self-launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure as well: per-stage, roofline and VALU figures, the eager "
+                         "drop-in figure, the index-exact section and the other workloads (--no-strict / --no-extra-workloads "
+                         "leave them out), the multi-GPU accounting and the CPU baseline (--no-cpu-baseline leaves it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): the images at a "
+                         "fixed sample of pixels, the loss if any, the gradients of the optimised tensors at a fixed sample of "
+                         "Gaussians (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.lean:
         args.graph = "off"
 
@@ -658,10 +708,19 @@ def main():
             from dn_splatter_amd import fused_loss
             loss_counts = fused_loss.depth_counts(batch["mono_depth"])
 
+    # --dump-outputs: the images (and loss) the latest step handed its caller, detached.  Under graph replay these are the tensors
+    # of the capture, which every replay overwrites; holding them keeps their memory from going back to the graph's pool.
+    last = {}
+
+    def keep(out, loss=None):
+        if args.dump_outputs is not None:
+            last.update({k: out[k].detach() for k in OUT_KEYS}, loss=None if loss is None else loss.detach())
+
     def step():
         for k in dp.GRAD_KEYS:
             gp[k].grad = None
         out = renderer.get_outputs(cam)
+        loss = None
         if batch is not None and args.losses == "fused":
             loss = fused_loss.dn_loss_fused(out, batch, gp["scales"], counts=loss_counts)
             (loss * loss_scale if loss_scale != 1.0 else loss).backward()
@@ -671,6 +730,7 @@ def main():
         else:
             # the losses stay in PyTorch (north star); their result is a dense cotangent per output image
             torch.autograd.backward([out[k] for k in OUT_KEYS], [cot[k] for k in OUT_KEYS])
+        keep(out, loss)
         return dp.allreduce_gradients(gp, arena, exchange=exchange)
 
     # "sum" reduction: the step's loss is the MEAN over the ranks' cameras, so every rank scales its own by 1 / world
@@ -688,31 +748,35 @@ def main():
             exchange.packed = False
             exchange.mine = exchange.gathered = None
             step()
-    # Stage breakdown: PROBE_STEPS fully instrumented steps OUTSIDE the timed region.  Bracketing all six stages with
+    # --full, stage breakdown: PROBE_STEPS fully instrumented steps OUTSIDE the timed region.  Bracketing all six stages with
     # HIP events costs ~80 us of stream time per frame (a ~6 us bubble per event pair, seen in the rocprofv3 timeline),
     # so the timed region below only brackets the dominant stage, whose live duration the roofline figure needs.
-    for _ in range(0 if args.lean else PREROLL_STEPS):      # the probes, too, are taken at operating clocks (see PREROLL_STEPS)
-        step()
-    torch.cuda.synchronize()
-    probe = _lib.StageTimer()
-    _lib.TIMER = probe
-    for _ in range(PROBE_STEPS):
-        step()
-    torch.cuda.synchronize()
-    _lib.TIMER = None
-    pstats = probe.summary()
+    pstats = {}
+    if args.full:
+        for _ in range(0 if args.lean else PREROLL_STEPS):      # the probes, too, are taken at operating clocks (see PREROLL_STEPS)
+            step()
+        torch.cuda.synchronize()
+        probe = _lib.StageTimer()
+        _lib.TIMER = probe
+        for _ in range(PROBE_STEPS):
+            step()
+        torch.cuda.synchronize()
+        _lib.TIMER = None
+        pstats = probe.summary()
 
     def stage_ms(st, name, steps):
         if name == "binning":
             return sum(st[k][2] for k in ("dnsplat_bin_prepare", "dnsplat_bin_emit_sort") if k in st) / max(steps, 1)
         return st[name][1] if name in st else None
 
-    probe_ms = {name: stage_ms(pstats, name, PROBE_STEPS) for name in STAGE_NAMES}
+    live = None
+    if args.full:
+        probe_ms = {name: stage_ms(pstats, name, PROBE_STEPS) for name in STAGE_NAMES}
     # ---- the EAGER drop-in figure (VERDICT r04 missing 4): what a maintainer gets who applies INTEGRATION.md under nerfstudio's
     # trainer — the same fused step launched kernel by kernel from Python through ctypes and autograd (~35 launches), no graph,
     # bin policy as given (default "deferred": the host never waits for the intersection count).  Pre-rolled like everything else.
     eager_drop_in = None
-    if world == 1 and not args.lean and not args.two_call and not args.torch_postops:
+    if args.full and world == 1 and not args.lean and not args.two_call and not args.torch_postops:
         from dn_splatter_amd import _ops as _ops_e
         for _ in range(PREROLL_STEPS):
             step()
@@ -733,21 +797,22 @@ def main():
                          "host_cpu_count": os.cpu_count()}
     # one step through the COUNTING instantiation of the compositing kernels (outside the timed region)
     counts = None
-    if not args.two_call and not args.torch_postops and not args.lean:
+    if args.full and not args.two_call and not args.torch_postops and not args.lean:
         from dn_splatter_amd import _ops
         _ops.PAIR_COUNTERS = torch.zeros(8, dtype=torch.int64, device=dev)
         step()
         torch.cuda.synchronize()
         counts = _ops.PAIR_COUNTERS.tolist()
         _ops.PAIR_COUNTERS = None
-    dominant = max((n for n in probe_ms if probe_ms[n] is not None), key=lambda n: probe_ms[n])
-    live = ("dnsplat_bin_prepare", "dnsplat_bin_emit_sort") if dominant == "binning" else (dominant,)
+    if args.full:
+        dominant = max((n for n in probe_ms if probe_ms[n] is not None), key=lambda n: probe_ms[n])
+        live = ("dnsplat_bin_prepare", "dnsplat_bin_emit_sort") if dominant == "binning" else (dominant,)
     dp.barrier()
     torch.cuda.synchronize()
     # ---- the step as a replayed HIP graph -------------------------------------------------------------------------------
-    # The bracket around the dominant stage is part of the graph: two one-thread kernels that append the device's wall clock to a
-    # ring (HIP events cannot be recorded into a graph under capture on ROCm 7.2).  Every replay of the timed region leaves its
-    # pair; the tick is calibrated below against HIP events around a stamped interval.
+    # --full: the bracket around the dominant stage is part of the graph: two one-thread kernels that append the device's wall
+    # clock to a ring (HIP events cannot be recorded into a graph under capture on ROCm 7.2).  Every replay of the timed region
+    # leaves its pair; the tick is calibrated below against HIP events around a stamped interval.
     gstep, graph_note, stamps, tick_ms = None, None, None, None
     # with an exchange step (N > 1 ranks, or DNSPLAT_FORCE_DIST=1): the compute is one graph, the collectives follow each replay
     # eagerly (graph.GraphedDpStep); a dense all-reduce (--dense-allreduce) keeps the eager step
@@ -761,17 +826,23 @@ def main():
             for k in dp.GRAD_KEYS:
                 gp[k].grad = None
             out = renderer.get_outputs(cam)
+            loss = None
             if batch is not None and args.losses == "fused":
-                fused_loss.dn_loss_fused(out, batch, gp["scales"], counts=loss_counts).backward()
+                loss = fused_loss.dn_loss_fused(out, batch, gp["scales"], counts=loss_counts)
+                loss.backward()
             elif batch is not None:
-                torch_losses.dn_loss(out, batch, gp["scales"], **torch_loss_kwargs(args.losses)).backward()
+                loss = torch_losses.dn_loss(out, batch, gp["scales"], **torch_loss_kwargs(args.losses))
+                loss.backward()
             else:
                 torch.autograd.backward([out[k] for k in OUT_KEYS], [cot[k] for k in OUT_KEYS])
+            keep(out, loss)
 
-        stamps = _lib.StampTimer(live, dev)
+        before_capture = None
+        if args.full:
+            stamps = _lib.StampTimer(live, dev)
 
-        def before_capture(c):
-            _lib.TIMER = stamps
+            def before_capture(c):
+                _lib.TIMER = stamps
 
         try:
             renderer.forget()          # the autograd graph of the last eager frame (its AccumulateGrad nodes live on the eager stream)
@@ -795,24 +866,25 @@ def main():
             def step():     # noqa: F811
                 gstep()
                 return 0
-    timer = _lib.StageTimer(only=live)
+    timer = _lib.StageTimer(only=live) if args.full else None
     _lib.TIMER = None
     wire = 0
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
+    stamped = gstep is not None and args.full
     # Python's cyclic garbage collector off for the timed region (as timeit does): a generation-2 pass over the interpreter's
     # objects stalls the host for ~10 ms, i.e. four frames' worth of launches — seen as single 10 ms steps in a 30-step run
     gc.collect()
     gc.disable()
-    # pre-roll (see PREROLL_STEPS); with the graph it doubles as the calibration interval of the stamp clock: HIP events around
-    # an interval that two extra stamps delimit
-    if gstep is not None:
+    # pre-roll (see PREROLL_STEPS); with the stamped graph it doubles as the calibration interval of the stamp clock: HIP events
+    # around an interval that two extra stamps delimit
+    if stamped:
         torch.cuda.synchronize()
         stamps.reset()
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         stamps.stamp(); c0.record()
     for _ in range(0 if args.lean else PREROLL_STEPS):
         step()
-    if gstep is not None:
+    if stamped:
         c1.record(); stamps.stamp()
         torch.cuda.synchronize()
         r = stamps.ring[:int(stamps.cursor.item())].tolist()
@@ -820,19 +892,21 @@ def main():
     _lib.TIMER = None
     for _ in range(args.warmup):
         step()
-    if gstep is not None:
+    if stamped:
         stamps.reset()
     _lib.TIMER = timer if gstep is None else None
     dp.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks:
+        marks[0].record()
     host_s = 0.0
     for i in range(args.steps):
         h0 = time.perf_counter()
         wire = step()
         host_s += time.perf_counter() - h0
-        marks[i + 1].record()
+        if marks:
+            marks[i + 1].record()
     torch.cuda.synchronize()
     from dn_splatter_amd import _ops as _ops_mod
     _ops_mod.verify_pending_counts(dev, block=True)     # "deferred" bin policy: every frame's intersection count checked inside the timed region
@@ -844,6 +918,32 @@ def main():
     gc.enable()
     _lib.TIMER = None
     elapsed = dp.max_over_ranks(elapsed, dev)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {k: last[k] for k in OUT_KEYS}, {k: gp[k].grad for k in dp.GRAD_KEYS}, last["loss"])
+
+    fps_total = world * args.steps / elapsed
+    res = {
+        "metric": "fwd+bwd frames/sec @1M Gaussians 1080p; HBM GB/s vs roofline",
+        "value": round(fps_total, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "launch": ("one HIP graph replay per step" if gstep is not None
+                   else "eager launches from Python" + (f" ({graph_note})" if graph_note else "")),
+        "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {N} random-init Gaussians, 1 camera/GPU {W}x{H}, SH degree 3 + "
+                               f"expected depth + per-Gaussian normals ({D_CH} channels, "
+                               f"{'two-call' if args.two_call else 'fused one-pass'}, post-ops in {'torch' if (args.torch_postops or args.two_call) else 'HIP'}), fx=fy={focal}, orbit r=8, "
+                               f"closed-form 3-NN scale init{'' if args.scene == 'reference_init' else ' perturbed: log-scales + N(0, 0.6), opacity logits + N(0, 2)'}, "
+                               f"{('dn-splatter loss stack (' + args.losses + ')') if args.losses else 'random dense cotangents'}",
+                   "scene": args.scene, "N": N, "pixels": P, "bin_policy": args.bin_policy,
+                   "allreduce_bytes_per_step": wire,
+                   "parallelism": (f"dp{world} (camera per GPU; per step {wire} B exchanged per GPU over RCCL: "
+                                   + ("geometry grads all-reduced, SH grads all-gathered as factors)" if exchange is not None
+                                      else "one all-reduce of the flat gradient bucket)")) if world > 1 else "single GPU"},
+    }
+    if not args.full:
+        finish(res if rank == 0 else None)
+        return
 
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     q = lambda f: round(per_step[min(len(per_step) - 1, int(f * len(per_step)))], 4)   # noqa: E731
@@ -936,7 +1036,6 @@ def main():
                                        "useful_frac": round(useful * f / t / 1e12 / VALU_PEAK_TFLOPS, 4),
                                        "useful_pair_fraction": round(useful / max(issued, 1), 4)}
     B = sum(sb.values())
-    fps_total = world * args.steps / elapsed
     frame_roofline = {"alg_bytes_per_frame": B, "alg_bytes_reference_rule": sum(sb_ref.values()),
                       "achieved_GBps": round(B * (args.steps / elapsed) / 1e9, 1),
                       "frac": round(B * (args.steps / elapsed) / 1e9 / HBM_PEAK_GBS, 4)}
@@ -1072,36 +1171,11 @@ def main():
                  "isects_max_over_mean": round(max(per_rank_I) / (sum(per_rank_I) / len(per_rank_I)), 4)}
 
     if rank == 0:
-        res = {
-            "metric": "fwd+bwd frames/sec @1M Gaussians 1080p; HBM GB/s vs roofline",
-            "value": round(fps_total, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        res.update({
             "gpu_ms_per_step_p10_p50_p90": [q(0.1), q(0.5), q(0.9)], "gpu_ms_per_step_max": round(per_step[-1], 4),
             "host_enqueue_ms_per_step": round(1e3 * host_s / args.steps, 4),
             "gpu_ms_per_step_series": [round(marks[i].elapsed_time(marks[i + 1]), 3) for i in range(args.steps)],
             "dominant_stage_ms_series": [round(x, 3) for x in live_ms] if live_ms else None,
-            "launch": ("one HIP graph replay per step; the dominant stage is bracketed inside the graph by device wall-clock stamps "
-                       f"(s_memrealtime, {1e6 * tick_ms:.3f} ns per tick calibrated against HIP events; {len(live_ms)} brackets in the "
-                       f"{args.steps} timed steps)") if gstep is not None
-                      else ("eager launches from Python" + (f" ({graph_note})" if graph_note else "")),
-            "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {N} random-init Gaussians, 1 camera/GPU {W}x{H}, SH degree 3 + "
-                                   f"expected depth + per-Gaussian normals ({D_CH} channels, "
-                                   f"{'two-call' if args.two_call else 'fused one-pass'}, post-ops in {'torch' if (args.torch_postops or args.two_call) else 'HIP'}), fx=fy={focal}, orbit r=8, "
-                                   f"closed-form 3-NN scale init{'' if args.scene == 'reference_init' else ' perturbed: log-scales + N(0, 0.6), opacity logits + N(0, 2)'}, "
-                                   f"{('dn-splatter loss stack (' + args.losses + ')') if args.losses else 'random dense cotangents'}",
-                       "scene": args.scene,
-                       "alpha_clamp_twin_active": (bool(int(info["_saturation_flag"].item())) if info.get("_saturation_flag") is not None else None),
-                       "N": N, "Nv": Nv, "n_isects": I, "n_isects_sorted": I_sorted, "mean_isects_per_rank": i_all / world,
-                       "mean_tile_list_len": round(I / T, 1), "pixels": P, "bin_policy": args.bin_policy,
-                       # every result row reports Nv, I and the mean number of Gaussians blended per pixel
-                       "mean_blended_gaussians_per_pixel": (round(counts[3] / P, 1) if counts else None),
-                       "allreduce_bytes_per_step": wire,
-                       "grads_in_flat_bucket": bool(all(arena.holds(gp[k].grad) for k in dp.GRAD_KEYS)),
-                       "parallelism": (f"dp{world} (camera per GPU; per step {wire} B exchanged per GPU over RCCL: "
-                                       + ("geometry grads all-reduced, SH grads all-gathered as factors)" if exchange is not None
-                                          else "one all-reduce of the flat gradient bucket)")) if world > 1 else "single GPU"},
             "roofline": roofline,
             "roofline_valu": roofline_valu,
             "frame_roofline": frame_roofline,
@@ -1111,7 +1185,19 @@ def main():
             "multi_gpu": multi,
             "stages": stages,
             "other_ms_torch_postops_autograd_host": round(1e3 * elapsed / args.steps - gpu_stage_ms, 4),
-        }
+        })
+        if gstep is not None:
+            res["launch"] = ("one HIP graph replay per step; the dominant stage is bracketed inside the graph by device wall-clock stamps "
+                             f"(s_memrealtime, {1e6 * tick_ms:.3f} ns per tick calibrated against HIP events; {len(live_ms)} brackets in the "
+                             f"{args.steps} timed steps)")
+        res["config"].update({
+            "alpha_clamp_twin_active": (bool(int(info["_saturation_flag"].item())) if info.get("_saturation_flag") is not None else None),
+            "Nv": Nv, "n_isects": I, "n_isects_sorted": I_sorted, "mean_isects_per_rank": i_all / world,
+            "mean_tile_list_len": round(I / T, 1),
+            # every result row reports Nv, I and the mean number of Gaussians blended per pixel
+            "mean_blended_gaussians_per_pixel": (round(counts[3] / P, 1) if counts else None),
+            "grads_in_flat_bucket": bool(all(arena.holds(gp[k].grad) for k in dp.GRAD_KEYS)),
+        })
         if world == 1 and not args.no_cpu_baseline:
             dns.set_grad_arena(None)
             dns.set_sh_exchange(None)
@@ -1120,8 +1206,13 @@ def main():
             except Exception as e:  # the baseline is reported, never required for the GPU number
                 res["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": os.cpu_count(), "kind": "port",
                                        "sample": f"failed: {e!r}"}
-    else:
-        res = None
+    finish(res if rank == 0 else None)
+
+
+def finish(res):
+    """Ends the run on every rank; rank 0 passes the result line and prints it."""
+    from dn_splatter_amd import dp
+
     dp.barrier()
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

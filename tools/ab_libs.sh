@@ -6,7 +6,7 @@ for v in "$@" "$1"; do
   export DNSPLAT_LIB=$R/gpurun_ab/lib_$v.so
   if [ -n "${CHECK:-}" ]; then timeout 900 python -m pytest tests -m gpu -x -q -k "$CHECK" 2>&1 | tail -2; fi
   for rep in 1 2; do
-    python bench.py --no-cpu-baseline --steps ${STEPS:-30} --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-cpu-baseline --steps ${STEPS:-30} --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 st=d['stages']

@@ -4,6 +4,7 @@
 #   /usr/local/graft/bin/gpurun --timeout 900 -- 'bash tools/pmc_traffic.sh'   ->  gpurun_out/pmc_traffic/
 #   other workloads: WORKLOAD=c3 BENCH_ARGS='--workload c3' bash tools/pmc_traffic.sh
 cd "${GRAFT_REPO_ROOT:-.}"; R=$(pwd); mkdir -p gpurun_out/pmc_traffic; export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"      # the bench with every step it ran when these counters were defined
 for c in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$R/gpurun_out/pmc_traffic/$c" -o p -- \
      python "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --lean ${BENCH_ARGS:-} > "$R/gpurun_out/pmc_traffic/$c.json" 2> "$R/gpurun_out/pmc_traffic/$c.err"); echo "$c rc=$?"

@@ -15,7 +15,7 @@ for w in ${PMC_WORKLOADS:-c2}; do
   cp gpurun_out/pmc_traffic/pmc_traffic.merged.json $O/pmc_traffic.merged.json; rm -rf gpurun_out/pmc_traffic
 done; fi
 echo "== bench (driver's command)"; t0=$(date +%s)
-python bench.py --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$? ($(( $(date +%s)-t0 )) s)"
+python bench.py --full --steps 20 --warmup 5 > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$? ($(( $(date +%s)-t0 )) s)"
 python - $O/bench_c2.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -27,12 +27,12 @@ print("valu", {k: v for k, v in (d.get("roofline_valu") or {}).items() if k.star
 PY
 echo "== the other ways in (INTEGRATION.md A / B): two drop-in calls inside the reference's op sequence; fused pass with torch post-ops"
 for m in --two-call --torch-postops; do
-  python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-strict --no-extra-workloads $m 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-strict --no-extra-workloads $m 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$m', d['value'], 'frames/s', d['ms_per_step'], 'ms |', d['launch'][:50])" | tee -a $O/bench_modes.txt
 done
 echo "== kernel stats"
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o trace -- python "$R/bench.py" --steps 40 --warmup 5 --no-cpu-baseline --lean > "$R/$O/prof_bench.json" 2> "$R/$O/prof.err"); echo "rocprof rc=$?"
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o trace -- python "$R/bench.py" --full --steps 40 --warmup 5 --no-cpu-baseline --lean > "$R/$O/prof_bench.json" 2> "$R/$O/prof.err"); echo "rocprof rc=$?"
 cp $(find $O/prof -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv 2>/dev/null; rm -rf $O/prof
 python - $O/kernel_stats.csv <<'PY'
 import csv, sys
@@ -41,17 +41,17 @@ for r in rows[:12]:
     print(f"{r['Name'][:90]:90s} n {r['Calls']:>4s} avg {float(r['AverageNs'])/1e3:8.1f} min {float(r['MinNs'])/1e3:8.1f} us {r['Percentage']}")
 PY
 echo "== frame timeline c2"
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$R/$O/prof3" -o trace -- python "$R/bench.py" --steps 6 --warmup 2 --no-cpu-baseline --lean > /dev/null 2> "$R/$O/prof3.err"); echo "rc=$?"
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$R/$O/prof3" -o trace -- python "$R/bench.py" --full --steps 6 --warmup 2 --no-cpu-baseline --lean > /dev/null 2> "$R/$O/prof3.err"); echo "rc=$?"
 f=$(find $O/prof3 -name '*kernel_trace.csv' | head -1); python tools/frame_timeline.py "$f" > $O/frame_timeline_c2.txt; rm -rf $O/prof3; tail -2 $O/frame_timeline_c2.txt
 echo "== one rank through RCCL (one slice: the default)"
-DNSPLAT_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-strict --no-extra-workloads > $O/bench_c2_single_rank_rccl.json 2>$O/rccl.err; echo "rc=$?"
+DNSPLAT_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-strict --no-extra-workloads > $O/bench_c2_single_rank_rccl.json 2>$O/rccl.err; echo "rc=$?"
 python - $O/bench_c2_single_rank_rccl.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print("rccl", d["value"], d["ms_per_step"], json.dumps(d.get("multi_gpu"))[:700])
 PY
 echo "== the whole --gpus 2 flow of bench.py with two REAL ranks sharing this GPU (gloo carries the collectives: RCCL refuses two ranks"
 echo "   per device) — not a performance figure: the N > 1 code path of the driver's scaling run, end to end, for the first time"
-DNSPLAT_DIST_BACKEND=gloo DNSPLAT_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 6 --warmup 2 > $O/bench_c2_two_ranks_one_gpu_gloo.json 2> $O/two_ranks.err; echo "rc=$?"
+DNSPLAT_DIST_BACKEND=gloo DNSPLAT_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 6 --warmup 2 > $O/bench_c2_two_ranks_one_gpu_gloo.json 2> $O/two_ranks.err; echo "rc=$?"
 python - $O/bench_c2_two_ranks_one_gpu_gloo.json <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ port=29520
 for w in c2 c5; do
   for mode in ${MODES:-auto rebuild packed own+packed}; do
     port=$((port+1))
-    MASTER_PORT=$port python bench.py --steps 20 --warmup 3 --no-cpu-baseline --workload $w --exchange $mode > $O/bench_${w}_${mode}.json 2> $O/bench_${w}_${mode}.err
+    MASTER_PORT=$port python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --workload $w --exchange $mode > $O/bench_${w}_${mode}.json 2> $O/bench_${w}_${mode}.err
     tail -1 $O/bench_${w}_${mode}.json | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); m=d['multi_gpu']
@@ -17,7 +17,7 @@ print('$w $mode |', d['value'], 'fps | step', m['step_ms'], 'compute_only', m['c
 done | tee $O/summary.txt
 for w in c5; do for mode in auto rebuild "rebuild --slices 4"; do
   port=$((port+1)); tag=$(echo $mode | tr -d ' -')
-  (cd /tmp && MASTER_PORT=$port timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$R/$O/prof_${w}_${tag}" -o trace -- python "$R/bench.py" --steps 6 --warmup 2 --no-cpu-baseline --lean --workload $w --exchange $mode > /dev/null 2> "$R/$O/prof_${w}_${tag}.err")
+  (cd /tmp && MASTER_PORT=$port timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$R/$O/prof_${w}_${tag}" -o trace -- python "$R/bench.py" --full --steps 6 --warmup 2 --no-cpu-baseline --lean --workload $w --exchange $mode > /dev/null 2> "$R/$O/prof_${w}_${tag}.err")
   f=$(find $O/prof_${w}_${tag} -name '*kernel_trace.csv' | head -1)
   [ -n "$f" ] && python tools/frame_timeline.py "$f" > $O/frame_timeline_single_rank_rccl_${w}_${tag}.txt 2>&1
   rm -rf $O/prof_${w}_${tag}

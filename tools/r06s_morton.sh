@@ -9,6 +9,6 @@ st=d['stages']
 print('$1 |', d['value'], 'fps', d['ms_per_step'], 'ms | ' + ' '.join('%s %.4f' % (k.replace('dnsplat_',''), v['ms']) for k, v in st.items()))"; }
 for w in c2 c3 c5; do
 for rep in 1 2; do
-run "$w reference_init" "--workload $w" ${w}_ref_$rep
-run "$w morton        " "--workload $w --scene morton" ${w}_morton_$rep
+run "$w reference_init" "--full --workload $w" ${w}_ref_$rep
+run "$w morton        " "--full --workload $w --scene morton" ${w}_morton_$rep
 done; done
