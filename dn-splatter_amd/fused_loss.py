@@ -220,6 +220,8 @@ class _ScaleRegFn(torch.autograd.Function):
         v = torch.empty_like(scales)
         total = torch.zeros((), dtype=torch.float32, device=scales.device)
         _lib.run("dnsplat_scale_reg", _lib.lib().dnsplat_scale_reg, N, _ptr(scales), 1.0 / max(N, 1), _ptr(v), _ptr(total), _stream())
+        if N == 0:
+            total.fill_(float("nan"))                       # the mean of no Gaussians: nan, as the reference's .mean()
         ctx.save_for_backward(v)
         return total
 
@@ -237,10 +239,18 @@ def scale_reg(scales: Tensor) -> Tensor:
 
 def dn_loss_fused(outputs: Dict[str, Tensor], batch: Dict[str, Tensor], scales: Tensor, ssim_lambda: float = 0.2,
                   depth_lambda: float = 0.2, depth_tolerance: float = 0.1, counts: Optional[Tensor] = None) -> Tensor:
-    """Drop-in for ``torch_losses.dn_loss`` (mono depth + mono normal supervision)."""
-    gt_depth = batch.get("mono_depth")
+    """Drop-in for ``torch_losses.dn_loss`` (mono depth + mono normal supervision).  A ``batch["mask"]`` multiplies the rendered
+    depth, both normals and the two ground truths before the launch, as dn_model.py:646-659 does (the rgb term does not see it);
+    ``counts`` (``depth_counts``) are then those of the MASKED ground-truth depth."""
+    depth, normal = outputs["depth"], outputs["normal"]
+    gt_depth, gt_normal = batch.get("mono_depth"), batch.get("normal")
+    if "mask" in batch:                                                             # dn_model.py:646-659
+        mask = batch["mask"]
+        depth, normal = depth * mask, normal * mask
+        gt_depth = gt_depth * mask if gt_depth is not None else None
+        gt_normal = gt_normal * mask if gt_normal is not None else None
     if gt_depth is not None and counts is None:
         counts = depth_counts(gt_depth, depth_tolerance)
-    per_pixel = _DnLossFn.apply(outputs["rgb"], outputs["depth"], outputs["normal"], batch["image"], gt_depth,
-                                batch.get("normal"), counts, ssim_lambda, depth_lambda, depth_tolerance)
+    per_pixel = _DnLossFn.apply(outputs["rgb"], depth, normal, batch["image"], gt_depth, gt_normal, counts, ssim_lambda,
+                                depth_lambda, depth_tolerance)
     return per_pixel + _ScaleRegFn.apply(scales)                                      # regularization_strategy.py:195-199

@@ -1,0 +1,483 @@
+"""The loss kernels (losses.hip) and the depth -> normal kernel (postops.hip) at the sizes training runs them, against the same
+PyTorch restatements evaluated in float64.
+
+The PyTorch side is ``torch_losses`` (pinned to the reference's own code by test_reference_golden.py) in float64 as the yardstick and
+in float32 for the envelope: where the fp32 restatement itself is far from exact arithmetic (SSIM sensitivities divide by the ~1e-4
+variances of smooth windows; the depth stencil subtracts two back-projected points ~10 apart that differ by ~0.02), no fp32 kernel
+can be asked to be closer than that.  Every cotangent: ``assert_close`` against fp64 with the fp32 envelope (at most a handful of
+entries may lean on it) and the per-pixel statistic (``check_pixels``).  Loss values: 1e-5 relative of fp64.
+
+Sizes: the two frame sizes of the benchmark, 1024 x 1024 (one trip of the grid-stride loops of edge_aware_logl1_kernel /
+tv_loss_kernel: 4096 workgroups x 256 lanes = 1 048 576 pixels) and 1025 x 1024 (the first frame that needs a second trip), and the
+minimal / ragged shapes of each kernel.  ``scale_reg``: N around one workgroup and around the 1024-workgroup cap (262 144), and 5 M.
+"""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from _scenes import FP32_ENVELOPE, PIX_MAX, PIX_P99, assert_close, check_pixels, fp64_envelope, row_rel_stats
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+GRAD_TOL = 2e-4          # gradients, relative to the tensor's scale: the constant of test_gpu_parity's loss tests
+VALUE_TOL = 1e-5         # loss values, relative to fp64
+# float32(0.1): the threshold the kernels and the fp32 restatement compare against (a Python 0.1 meets an fp32 tensor as 0.1f).
+# The fp64 evaluation takes the same number, so that a ground truth of exactly 0.1f is invalid on every side.
+TOL_F32 = float(torch.tensor(0.1, dtype=torch.float32))
+
+FULL = [(1920, 1080), (1600, 1200)]
+GRID = [(1024, 1024), (1025, 1024)]
+
+
+# ---- inputs ----------------------------------------------------------------------------------------------------------------------
+
+
+@functools.lru_cache(maxsize=1)
+def _c2_scene():
+    from dn_splatter_amd import synthetic
+
+    return synthetic.make_gauss_params(1_000_000, sh_rest_std=0.1, seed=0, device=DEV)
+
+
+@functools.lru_cache(maxsize=8)
+def _render(W, H, view):
+    """rgb, depth, normal of the C2 scene (1 M Gaussians) seen from orbit camera ``view`` at W x H (float32, on the device)."""
+    import dn_splatter_amd as dns
+    from dn_splatter_amd import synthetic
+
+    with torch.no_grad():
+        out = dns.DNSplatterRenderer(_c2_scene(), fused=True).get_outputs(synthetic.orbit_camera(view, width=W, height=H).to(DEV))
+    return tuple(out[k].detach().float().contiguous() for k in ("rgb", "depth", "normal", "accumulation"))
+
+
+def _frame(W, H, content, seed=0):
+    """(outputs, batch): prediction and ground truth of one training step, float32 on the device.
+    ``render``: the renderer's own frames — prediction from orbit camera 0, ground truth from its neighbour, camera 1 (the smooth,
+    low-variance windows of real training); ``noise``: uniform noise.  Both carry the edges where a kernel goes wrong: a flat block
+    (zero-variance windows, pred == gt, equal neighbours: sgn(0) = 0 bit for bit), an image block below 10/255, ground-truth depth
+    at and just below the 0.1 tolerance and just above it."""
+    g = torch.Generator().manual_seed(seed)
+    if content == "render":
+        rgb, depth, normal, _ = _render(W, H, 0)
+        img, gdepth, gnormal, _ = _render(W, H, 1)
+        out = {"rgb": rgb.clone(), "depth": depth.clone(), "normal": normal.clone()}
+        batch = {"image": img.clone(), "mono_depth": gdepth.clone(), "normal": gnormal.clone()}
+    else:
+        r = lambda *s: torch.rand(*s, generator=g).to(DEV)      # noqa: E731
+        out = {"rgb": r(H, W, 3), "depth": r(H, W, 1) * 9 + 0.2, "normal": r(H, W, 3)}
+        batch = {"image": r(H, W, 3), "mono_depth": r(H, W, 1) * 9 + 0.5, "normal": r(H, W, 3)}
+    h3, w3 = max(H // 3, 1), max(W // 3, 1)
+    # flat block: the same constant in prediction and ground truth
+    for k, b in (("rgb", "image"), ("normal", "normal")):
+        out[k][:h3, :w3] = 0.5
+        batch[b][:h3, :w3] = 0.5
+    out["depth"][:h3, :w3] = 3.0
+    batch["mono_depth"][:h3, :w3] = 3.0
+    # dark block: image below 10 / 255 (the edge weights clamp it)
+    batch["image"][h3:2 * h3, :w3] = torch.rand(min(h3, H - h3), w3, 3, generator=g).to(DEV) * (8 / 255)
+    out["rgb"][h3:2 * h3, :w3] = batch["image"][h3:2 * h3, :w3] + 1e-3
+    # depth ground truth around the tolerance: at it, below it, zero, just above it
+    gd = batch["mono_depth"]
+    c = 2 * w3
+    gd[:h3, w3:c] = TOL_F32
+    gd[h3:2 * h3, w3:c] = 0.05
+    gd[2 * h3:, w3:c] = 0.0
+    gd[:h3, c:] = float(torch.nextafter(torch.tensor(TOL_F32), torch.tensor(1.0)))
+    return out, batch
+
+
+def _mask(H, W, seed=3):
+    """[H,W,1] float 0/1 mask (dn_model.py:646-659 multiplies by it): random pixels and a masked-out band."""
+    m = (torch.rand(H, W, 1, generator=torch.Generator().manual_seed(seed)) > 0.2).float()
+    m[H // 2:H // 2 + max(H // 8, 1)] = 0.0
+    return m.to(DEV)
+
+
+# ---- comparisons -----------------------------------------------------------------------------------------------------------------
+
+
+def _grads(fn, out, batch, scales, dtype):
+    """value and gradients w.r.t. every rendered image (and the scales) of fn(outputs, batch, scales) evaluated in ``dtype``."""
+    o = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in out.items()}
+    b = {k: v.to(dtype) for k, v in batch.items()}
+    sc = scales.detach().to(dtype).clone().requires_grad_(True)
+    loss = fn(o, b, sc)
+    loss.backward()
+    return loss.detach(), {**{k: v.grad for k, v in o.items()}, "scales": sc.grad}
+
+
+def _check_value(v, v64, what, v32=None):
+    """within VALUE_TOL of fp64, plus the fp32 envelope of the restatement's value where one is given (the SSIM of a single noisy
+    11 x 11 window is ~0.03: its fp32 rounding alone is ~1e-5 of it)."""
+    v, v64 = float(v), float(v64)
+    env = 0.0 if v32 is None else FP32_ENVELOPE * abs(float(v32) - v64)
+    err = abs(v - v64)
+    print(f"[losses] {what}: value {v:.9g} vs fp64 {v64:.9g}: relative error {err / abs(v64):.2e} (fp32 envelope {env / abs(v64):.2e})")
+    assert err <= VALUE_TOL * abs(v64) + env, f"{what}: value {v!r} vs fp64 {v64!r} (relative {err / abs(v64):.2e} > {VALUE_TOL:.0e})"
+
+
+def _check_grad(hip, g64, g32, what, tol=GRAD_TOL, pixels=True):
+    """assert_close against fp64 with the fp32 envelope, then per pixel: the p99 and the largest of the row-relative error over
+    each pixel's channels (check_pixels) within PIX_P99 / PIX_MAX, or within 2 x FP32_ENVELOPE x the same statistic of the fp32
+    restatement where that is larger (two fp32 evaluations, each within the envelope of exact arithmetic, may sit on opposite sides of
+    it: measured up to 1.1 x FP32_ENVELOPE, at the largest pixel error of the 1080p rendered frame).  The SSIM part of d loss / d rgb is where it is: on a rendered frame the fp32 restatement's
+    own per-pixel error reaches percents at a few pixels of smooth windows (sensitivities divided by ~1e-4 variances)."""
+    assert_close(hip, g64, what, tol, envelope=fp64_envelope(g32, g64))
+    if pixels and hip.dim() == 3:
+        st = row_rel_stats(g32, g64)
+        p99, rmax = (PIX_P99, PIX_MAX) if st is None else (max(PIX_P99, 2 * FP32_ENVELOPE * st[1]), max(PIX_MAX, 2 * FP32_ENVELOPE * st[2]))
+        if st is not None:
+            print(f"[losses] {what}: the fp32 restatement per pixel: p99 {st[1]:.2e}  max {st[2]:.2e}")
+        check_pixels(hip, g64, what + " per pixel", enforce=True, p99=p99, rmax=rmax)
+
+
+def _check_loss(fn_hip, fn_ref, out, batch, scales, what, keys=("rgb", "depth", "normal", "scales")):
+    v, g = _grads(fn_hip, out, batch, scales, torch.float32)
+    v64, g64 = _grads(fn_ref(TOL_F32), out, batch, scales, torch.float64)
+    _, g32 = _grads(fn_ref(0.1), out, batch, scales, torch.float32)
+    _check_value(v, v64, what)
+    for k in keys:
+        _check_grad(g[k], g64[k], g32[k], f"{what}: d loss / d {k}", tol=1e-6 if k == "scales" else GRAD_TOL)
+    return g
+
+
+def _fused(**kw):
+    from dn_splatter_amd.fused_loss import dn_loss_fused
+
+    return lambda o, b, s: dn_loss_fused(o, b, s, **kw)
+
+
+def _torch_stack(**kw):
+    from dn_splatter_amd import torch_losses as tl
+
+    return lambda tol: (lambda o, b, s: tl.dn_loss(o, b, s, depth_tolerance=tol, **kw))
+
+
+def _scales(N=500, seed=0):
+    return (torch.rand(N, 3, generator=torch.Generator().manual_seed(seed)) * 6 - 6).to(DEV)
+
+
+# ---- dn_loss_fused (dnsplat_dn_loss + dnsplat_scale_reg) ------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("content", ["render", "noise"])
+@pytest.mark.parametrize("W,H", FULL + [(1025, 1024), (43, 27), (11, 11), (12, 11), (11, 12)])
+def test_fused_loss_matches_fp64(dns, W, H, content):
+    """dn_loss_fused == torch_losses.dn_loss in fp64: with depth and normal supervision, and with the rgb term only."""
+    out, batch = _frame(W, H, content, seed=W + H)
+    sc = _scales()
+    _check_loss(_fused(), _torch_stack(), out, batch, sc, f"dn_loss_fused {W}x{H} {content}")
+    g = _check_loss(_fused(), _torch_stack(), out, {"image": batch["image"]}, sc, f"dn_loss_fused rgb only {W}x{H} {content}",
+                    keys=("rgb",))
+    assert float(g["depth"].abs().max()) == 0.0 and float(g["normal"].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("W,H", [FULL[0], (43, 27)])
+def test_fused_loss_with_a_mask_matches_fp64(dns, W, H):
+    """batch["mask"] multiplies depth, both normals and both ground truths (dn_model.py:646-659) on both sides."""
+    out, batch = _frame(W, H, "render" if W > 100 else "noise", seed=7)
+    batch["mask"] = _mask(H, W)
+    _check_loss(_fused(), _torch_stack(), out, batch, _scales(), f"dn_loss_fused masked {W}x{H}")
+
+
+@pytest.mark.parametrize("W,H", [FULL[1], (1025, 1024)])
+def test_hip_modules_stack_matches_fp64(dns, W, H):
+    """The reference's loss stack with the three modules install_losses swaps (SSIM, EdgeAwareLogL1, TVLoss) and the min-scale term
+    on HIP, the rest in PyTorch: dn_loss(..., ssim_impl="hip", hip_modules=True) == the plain stack in fp64, with and without a mask."""
+    from dn_splatter_amd import torch_losses as tl
+
+    out, batch = _frame(W, H, "render", seed=5)
+    hip = lambda o, b, s: tl.dn_loss(o, b, s, ssim_impl="hip", hip_modules=True)      # noqa: E731
+    _check_loss(hip, _torch_stack(), out, batch, _scales(), f"hip-modules stack {W}x{H}")
+    batch["mask"] = _mask(H, W)
+    _check_loss(hip, _torch_stack(), out, batch, _scales(), f"hip-modules stack masked {W}x{H}")
+
+
+def test_fused_loss_without_valid_depth_is_nan(dns):
+    """A depth ground truth at or below the tolerance everywhere: both EdgeAwareLogL1 means are over no pixels — nan, as the
+    reference's term_x[mask].mean()."""
+    from dn_splatter_amd import torch_losses as tl
+
+    out, batch = _frame(64, 48, "noise", seed=1)
+    batch["mono_depth"].fill_(0.05)
+    v = _fused()(out, batch, _scales())
+    want = tl.dn_loss({k: x.double() for k, x in out.items()}, {k: x.double() for k, x in batch.items()}, _scales().double(),
+                      depth_tolerance=TOL_F32)
+    assert torch.isnan(want) and torch.isnan(v.detach()), (float(v), float(want))
+
+
+# ---- SSIM (dnsplat_ssim) ----------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("content", ["render", "noise"])
+@pytest.mark.parametrize("W,H", FULL + [(43, 27), (11, 11), (12, 11), (11, 12)])
+def test_ssim_matches_fp64(dns, W, H, content):
+    """ssim_hip and the module form (fused_loss.SSIM, as splatfacto calls it) == torch_losses.ssim in fp64."""
+    from dn_splatter_amd import torch_losses as tl
+    from dn_splatter_amd.fused_loss import SSIM, ssim_hip
+
+    out, batch = _frame(W, H, content, seed=11 + W)
+    pred, gt = out["rgb"], batch["image"]
+
+    def ref(dtype):
+        x = pred.detach().to(dtype).clone().requires_grad_(True)
+        s = tl.ssim(x, gt.to(dtype))
+        s.backward()
+        return s.detach(), x.grad
+
+    s64, g64 = ref(torch.float64)
+    s32, g32 = ref(torch.float32)
+    x = pred.clone().requires_grad_(True)
+    s = ssim_hip(x, gt)
+    s.backward()
+    _check_value(s.detach(), s64, f"ssim {W}x{H} {content}", v32=s32)
+    _check_grad(x.grad, g64, g32, f"d ssim / d pred {W}x{H} {content}")
+    x2 = pred.clone().requires_grad_(True)
+    s2 = SSIM()(gt.permute(2, 0, 1)[None], x2.permute(2, 0, 1)[None])
+    s2.backward()
+    assert torch.equal(x2.grad, x.grad)                 # the value is a sum of fp32 atomics: equal up to their order
+    assert abs(float(s2.detach()) - float(s.detach())) <= 1e-6 * abs(float(s.detach()))
+
+
+# ---- EdgeAwareLogL1 (dnsplat_edge_aware_logl1) ------------------------------------------------------------------------------------
+
+
+def _depth_case(W, H, seed):
+    """pred, gt [H,W,1], image [H,W,3], validity mask [H,W,1]: noise with ties (pred == gt), equal image neighbours, a dark block
+    and depth at the tolerance."""
+    g = torch.Generator().manual_seed(seed)
+    pred = torch.rand(H, W, 1, generator=g) * 9 + 0.2
+    gt = torch.rand(H, W, 1, generator=g) * 9 + 0.5
+    rgb = torch.rand(H, W, 3, generator=g)
+    tie = torch.rand(H, W, 1, generator=g) < 0.1
+    pred[tie] = gt[tie]
+    rgb[:, : max(W // 4, 1)] = 0.25                                         # equal neighbours: edge weight exactly 1
+    rgb[: max(H // 4, 1)] = torch.rand(max(H // 4, 1), W, 3, generator=g) * (8 / 255)
+    gt[torch.rand(H, W, 1, generator=g) < 0.1] = TOL_F32
+    return pred.to(DEV), gt.to(DEV), rgb.to(DEV), (gt > TOL_F32).to(DEV)
+
+
+EDGE_SIZES = GRID + FULL + [(2, 2), (2, 1000), (1000, 2)]
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("W,H", EDGE_SIZES)
+def test_edge_aware_logl1_matches_fp64(dns, W, H, masked):
+    """fused_loss.EdgeAwareLogL1 == torch_losses.edge_aware_log_l1 (the reference's boolean-mask gather) in fp64, value and
+    gradient, with the validity mask DNRegularization passes and without one."""
+    from dn_splatter_amd import torch_losses as tl
+    from dn_splatter_amd.fused_loss import EdgeAwareLogL1
+
+    pred, gt, rgb, valid = _depth_case(W, H, seed=W * 7 + H)
+    mask = valid if masked else None
+
+    def ref(dtype):
+        x = pred.detach().to(dtype).clone().requires_grad_(True)
+        v = tl.edge_aware_log_l1(x, gt.to(dtype), rgb.to(dtype), mask)
+        v.backward()
+        return v.detach(), x.grad
+
+    v64, g64 = ref(torch.float64)
+    _, g32 = ref(torch.float32)
+    x = pred.clone().requires_grad_(True)
+    v = EdgeAwareLogL1()(x, gt, rgb, mask)
+    v.backward()
+    what = f"EdgeAwareLogL1 {W}x{H}{' masked' if masked else ''}"
+    _check_value(v.detach(), v64, what)
+    _check_grad(x.grad, g64, g32, "d " + what + " / d pred")
+
+
+def test_edge_aware_logl1_of_an_empty_mask_is_nan(dns):
+    from dn_splatter_amd import torch_losses as tl
+    from dn_splatter_amd.fused_loss import EdgeAwareLogL1
+
+    pred, gt, rgb, _ = _depth_case(64, 48, seed=2)
+    empty = torch.zeros(48, 64, 1, dtype=torch.bool, device=DEV)
+    assert torch.isnan(tl.edge_aware_log_l1(pred.double(), gt.double(), rgb.double(), empty))
+    assert torch.isnan(EdgeAwareLogL1()(pred, gt, rgb, empty).detach())
+
+
+# ---- TVLoss (dnsplat_tv_loss) -----------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("C", [1, 3, 4])
+@pytest.mark.parametrize("W,H", EDGE_SIZES)
+def test_tv_loss_matches_fp64(dns, W, H, C):
+    """fused_loss.TVLoss == torch_losses.tv_loss in fp64: noise with a constant block and runs of equal neighbours (sgn(0) = 0)."""
+    from dn_splatter_amd import torch_losses as tl
+    from dn_splatter_amd.fused_loss import TVLoss
+
+    g = torch.Generator().manual_seed(W + 3 * H + C)
+    pred = torch.rand(H, W, C, generator=g)
+    pred[: max(H // 3, 1), : max(W // 3, 1)] = 0.5
+    pred[:, 1::5] = pred[:, 0:-1:5][:, : pred[:, 1::5].shape[1]]           # every fifth column equals its left neighbour
+    pred = pred.to(DEV)
+
+    def ref(dtype):
+        x = pred.detach().to(dtype).clone().requires_grad_(True)
+        v = tl.tv_loss(x)
+        v.backward()
+        return v.detach(), x.grad
+
+    v64, g64 = ref(torch.float64)
+    _, g32 = ref(torch.float32)
+    x = pred.clone().requires_grad_(True)
+    v = TVLoss()(x)
+    v.backward()
+    _check_value(v.detach(), v64, f"TVLoss {W}x{H}x{C}")
+    _check_grad(x.grad, g64, g32, f"d TVLoss {W}x{H}x{C} / d pred")
+
+
+# ---- min-scale term (dnsplat_scale_reg) -------------------------------------------------------------------------------------------
+
+
+def _scale_rows(N, seed):
+    """[N,3] log-scales: isotropic rows (the synthetic / bench initialisation: an exact three-way tie), rows with two components
+    tied (at the minimum or above it), typical log-scales in (-6, 0), and rows whose exp underflows to 0 in fp32."""
+    g = torch.Generator().manual_seed(seed)
+    s = torch.rand(N, 3, generator=g) * 6 - 6
+    kind = torch.randint(0, 6, (N,), generator=g)
+    a = torch.rand(N, generator=g) * 6 - 6
+    b = a + torch.rand(N, generator=g) * 2 + 1e-3
+    iso, pos = kind == 0, torch.randint(0, 3, (N,), generator=g)
+    s[iso] = a[iso, None].expand(-1, 3)
+    for p in range(3):                                                       # two tied at the minimum, the third (larger) at p
+        sel = (kind == 1) & (pos == p)
+        s[sel] = a[sel, None].expand(-1, 3).clone()
+        s[sel, p] = b[sel]
+        sel = (kind == 2) & (pos == p)                                     # two tied ABOVE the minimum, which sits at p
+        s[sel] = b[sel, None].expand(-1, 3).clone()
+        s[sel, p] = a[sel]
+    und = kind == 3
+    s[und] = torch.rand(int(und.sum()), 3, generator=g) * -20 - 110          # exp(-110 .. -130) == 0 in fp32: a three-way tie at 0
+    mixed = kind == 4
+    s[mixed, 0] = -120.0                                                     # one component underflows, the others do not
+    if N:
+        s[0] = torch.tensor([-2.0, -2.0, -2.0])
+    return s.to(DEV)
+
+
+@pytest.mark.parametrize("N", [1, 255, 256, 257, 262_144, 262_145, 5_000_000])
+def test_scale_reg_matches_fp64_and_picks_torch_min_component(dns, N):
+    """scale_reg: mean_g min_k exp(s_gk) within 1e-5 of fp64; its gradient within 1e-6 of fp64 (the constant of the existing loss
+    test), and it lands on exactly the component fp32 torch.min on the device picks (ties: the first minimal one) — the reference
+    evaluates the term in fp32, so fp32 decides which component a tie resolves to."""
+    from dn_splatter_amd.fused_loss import scale_reg
+
+    s = _scale_rows(N, seed=N)
+
+    def ref(dtype):
+        x = s.detach().to(dtype).clone().requires_grad_(True)
+        v = torch.min(torch.exp(x), dim=1, keepdim=True)[0].mean()             # regularization_strategy.py:195-199
+        v.backward()
+        return v.detach(), x.grad
+
+    v64, g64 = ref(torch.float64)
+    _, g32 = ref(torch.float32)
+    x = s.clone().requires_grad_(True)
+    v = scale_reg(x)
+    v.backward()
+    _check_value(v.detach(), v64, f"scale_reg N={N}")
+    assert_close(x.grad, g64, f"d scale_reg / d scales N={N}", 1e-6, envelope=fp64_envelope(g32, g64))
+    got, want = x.grad != 0, g32 != 0
+    assert torch.equal(got, want), f"N={N}: the gradient lands on another component than torch.min's in " \
+                                   f"{int((got != want).any(dim=1).sum())} rows"
+    assert int(want.sum(dim=1).max()) <= 1
+
+
+def test_scale_reg_of_no_gaussians_is_nan(dns):
+    from dn_splatter_amd.fused_loss import scale_reg
+
+    x = torch.zeros(0, 3, device=DEV, requires_grad=True)
+    v = scale_reg(x)
+    assert torch.isnan(torch.min(torch.exp(x.detach()), dim=1, keepdim=True)[0].mean())
+    assert torch.isnan(v.detach()), float(v)
+    v.backward()
+    assert x.grad.shape == (0, 3)
+
+
+# ---- depth -> surface normal (dnsplat_dn_depth_normals) ---------------------------------------------------------------------------
+
+
+def _restated_surface_normal(depth, alphas, fx, fy, cx, cy, dtype):
+    """dn_model.py:533-537 (alpha == 0: the image-wide maximum depth) and :589-603 through model.normal_from_depth_image."""
+    from dn_splatter_amd import model
+
+    H, W = depth.shape
+    d = depth.to(dtype)
+    filled = torch.where(alphas > 0, d, d.max())
+    if dtype == torch.float32:
+        n = model.normal_from_depth_image(filled[..., None], fx, fy, cx, cy, (W, H), torch.eye(4, device=depth.device))
+    else:                       # the same back-projection (c2w = identity) in float64: normal_from_depth_image computes in float32
+        gx = torch.arange(W, dtype=dtype, device=depth.device)[None, :] + 0.5
+        gy = torch.arange(H, dtype=dtype, device=depth.device)[:, None] + 0.5
+        n = model.pcd_to_normal(torch.stack([(gx - cx) * filled / fx, (gy - cy) * filled / fy, filled], dim=-1))
+    n = n @ torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=dtype, device=depth.device))
+    return filled, (1 + n) / 2
+
+
+@pytest.mark.parametrize("workload", ["c2", "c3"])
+def test_depth_normals_match_fp64(dns, workload):
+    """dnsplat_dn_depth_normals on a rendered depth (the C2 / C3 scene at its full frame) with alpha == 0 regions added: the fill
+    bit for bit, the one-pixel border exactly 0.5, the normal image within 5e-6 + the fp32 envelope of the restatement."""
+    from dn_splatter_amd import _lib, _ops, synthetic
+
+    N, W, H = {"c2": (1_000_000, 1920, 1080), "c3": (3_000_000, 1600, 1200)}[workload]
+    cam = synthetic.orbit_camera(0, width=W, height=H)
+    if workload == "c2":
+        _, depth, _, acc = _render(W, H, 0)
+    else:
+        gp = synthetic.make_gauss_params(N, sh_rest_std=0.1, seed=0, device=DEV)
+        with torch.no_grad():
+            out = dns.DNSplatterRenderer(gp, fused=True).get_outputs(cam.to(DEV))
+        depth, acc = out["depth"].detach(), out["accumulation"].detach()
+        del gp, out
+    depth = depth.reshape(H, W).clone()
+    alphas = acc.reshape(H, W).clone()
+    # empty regions as an image of few Gaussians has them: a block, a stripe along the border, scattered pixels; their raw depth is 0
+    g = torch.Generator().manual_seed(9)
+    empty = torch.zeros(H, W, dtype=torch.bool)
+    empty[H // 4:H // 2, W // 5:W // 3] = True
+    empty[:, W - 40:] = True
+    empty |= torch.rand(H, W, generator=g) < 0.01
+    empty = empty.to(DEV)
+    alphas[empty] = 0.0
+    depth[empty] = 0.0
+    dmax = depth.max().reshape(1).contiguous()
+    depth_out = torch.empty_like(depth)
+    sn = torch.empty(H, W, 3, device=DEV)
+    _lib.check(_lib.lib().dnsplat_dn_depth_normals(W, H, cam.fx, cam.fy, cam.cx, cam.cy, _ops._ptr(depth), _ops._ptr(alphas),
+                                                   _ops._ptr(dmax), _ops._ptr(depth_out), _ops._ptr(sn), _ops._stream()),
+               "dnsplat_dn_depth_normals")
+    torch.cuda.synchronize()
+    filled32, sn32 = _restated_surface_normal(depth, alphas, cam.fx, cam.fy, cam.cx, cam.cy, torch.float32)
+    _, sn64 = _restated_surface_normal(depth, alphas, cam.fx, cam.fy, cam.cx, cam.cy, torch.float64)
+    assert torch.equal(depth_out, filled32)
+    border = torch.ones(H, W, dtype=torch.bool, device=DEV)
+    border[1:-1, 1:-1] = False
+    assert bool((sn[border] == 0.5).all())
+    # The restatement's fp32 error is cancellation in (x +- 1 - cx) d / fx away from the image centre (up to ~5e-5 at fx = 1200).
+    # The kernel rounds the same products but multiplies by 1 / fx instead of dividing, so at a given entry the two fp32 errors need
+    # not be alike even where their sizes are: the envelope is the restatement's worst error over the pixel's 3 x 3 stencil support
+    # and its channels (a pixel-by-pixel envelope leaves the kernel ~4x over it at a few thousand entries of a 1080p frame).
+    e32 = (sn32.double() - sn64).abs().amax(dim=-1)[None, None]
+    env = FP32_ENVELOPE * F.max_pool2d(e32, 3, 1, 1)[0, 0][..., None]
+    d = (sn.double() - sn64).abs()
+    allow = 5e-6 + env
+    ratio = float((d / allow).max())
+    print(f"[losses] surface normal {workload}: max error {float(d.max()):.2e} (fp32 restatement {float(e32.max()):.2e}); "
+          f"{int((d > 5e-6).sum())} of {d.numel()} entries beyond the 5e-6 floor; worst error / allowance {ratio:.3f}")
+    _log_margin(f"surface normal {workload}", ratio, float(d.max()) / 5e-6)
+    assert ratio <= 1.0, f"surface normal {workload}: worst error / (5e-6 + fp32 envelope) = {ratio:.2f}"
+
+
+def _log_margin(what, worst, strict):
+    import os
+
+    log = os.environ.get("DNSPLAT_MARGIN_LOG")
+    if log:
+        with open(log, "a") as f:
+            f.write(f"{os.environ.get('PYTEST_CURRENT_TEST', '?').split(' ')[0]}\t{what}\t{worst:.3f}\t{strict:.3f}\n")

@@ -444,6 +444,17 @@ def test_hip_fused_loss_equals_the_reference_combination():
     for got, key in ((gd, "loss_dict_v_depth"), (gn, "loss_dict_v_normal"), (gs, "loss_dict_v_scales")):
         ref = t(key)
         assert float((got.cpu() - ref).abs().max()) <= 1e-5 * max(1.0, float(ref.abs().max())), key
+    # with a mask in the batch: depth, both normals and both ground truths multiplied by it (dn_model.py:646-659)
+    pd3, pn3 = t("pred_depth").to(dev).requires_grad_(True), t("pred_normal").to(dev).requires_grad_(True)
+    out3 = {"rgb": rgb, "depth": pd3, "normal": pn3}
+    loss3 = fused_loss.dn_loss_fused(out3, dict(batch, mask=t("mask").to(dev)), sc)
+    reg3 = float(loss3.detach()) - float(tl.rgb_term({k: v.detach() for k, v in out3.items()}, batch))
+    want3 = float(g["masked_main"]) - float(g["loss_dict_rgb_term"])
+    assert abs(reg3 - want3) < 2e-5, (reg3, want3)
+    gd3, gn3 = torch.autograd.grad(loss3, [pd3, pn3])
+    for got, key in ((gd3, "masked_v_depth"), (gn3, "masked_v_normal")):
+        ref = t(key)
+        assert float((got.cpu() - ref).abs().max()) <= 1e-5 * max(1.0, float(ref.abs().max())), key
 
 
 # ------------------------------------------------------------------------------------------------------------------
