@@ -499,3 +499,50 @@ def assert_in_hull(grads, lo, hi, what, tol=REL_TOL, scales=None):
         worst = max(worst, w)
         assert w <= 1.0, f"{what} {k}: {int((viol > tol * scale).sum())} entries outside the hull by more than 1e-4 x scale, worst {w:.2f}"
     return worst
+
+
+def oracle_threads():
+    """Threads for the oracle's OpenMP loops: its gradient scatter uses omp atomics, and beyond ~32 threads it only gets slower
+    (bench.py cpu_baseline).  os.cpu_count() counts the whole host; OMP_NUM_THREADS, where set, is what this process may use."""
+    n = os.cpu_count() or 1
+    env = os.environ.get("OMP_NUM_THREADS", "").strip()
+    if env.isdigit() and int(env) > 0:
+        n = min(n, int(env))
+    torch.set_num_threads(min(32, n))
+
+
+def assert_binning_properties(info, cam=0):
+    """The tile lists of one camera of a product frame (``last_info`` of DNSplatterRenderer) without a reference list: status word 0,
+    sum(tiles_bin) = n_isects, non-decreasing offsets, every list (depth, index)-sorted, every Gaussian exactly tiles_bin times and only
+    in tiles of its gsplat box.  Holds for gsplat's boxes and for the tight ones (whose lists are sub-lists of gsplat's)."""
+    from dn_splatter_amd import _ops
+
+    dev = info["flatten_ids"].device
+    assert _ops.binning_status(info["_binning"], info["radii"].numel()) == 0, "a look-back wait of the tile sort timed out"
+    n = info["n_isects"]
+    tiles = info["tiles_bin"][cam].long()          # the count the binning walked (== tiles_per_gauss unless tight tile boxes)
+    assert int(tiles.sum()) == n, "sum(tiles_bin) != n_isects"
+    if info.get("tight_tiles"):     # a visible Gaussian may reach alpha >= 1/255 at no pixel centre at all
+        assert int(((tiles > 0) & ~(info["radii"][cam] > 0)).sum()) == 0
+    else:
+        assert int(((info["radii"][cam] > 0) != (tiles > 0)).sum()) == 0
+    offs = info["isect_offsets"].reshape(-1).long()
+    assert int(offs[0]) == 0 and bool((offs[1:] >= offs[:-1]).all()) and int(offs[-1]) <= n
+    # every tile list is depth-sorted, ties broken by Gaussian index (stable sort, Appendix A.3)
+    fid = info["flatten_ids"].long()
+    d = info["depths"][cam][fid]
+    tile_of = torch.searchsorted(offs, torch.arange(n, device=dev), right=True) - 1
+    same = tile_of[1:] == tile_of[:-1]
+    ok = (d[1:] > d[:-1]) | ((d[1:] == d[:-1]) & (fid[1:] > fid[:-1]))
+    assert bool((ok | ~same).all()), "a tile list is not (depth, index)-sorted"
+    # each Gaussian appears exactly tiles_bin times
+    cnt = torch.bincount(fid, minlength=tiles.shape[0])
+    assert torch.equal(cnt, tiles)
+    # and only in tiles of its bounding box (A.3)
+    xy = info["means2d"][cam][fid]
+    r = info["radii"][cam][fid].float()
+    tw = info["tile_width"]
+    tx, ty = (tile_of % tw).float(), (tile_of // tw).float()
+    inside = (tx >= torch.floor((xy[:, 0] - r) / 16)) & (tx < torch.ceil((xy[:, 0] + r) / 16)) & \
+             (ty >= torch.floor((xy[:, 1] - r) / 16)) & (ty < torch.ceil((xy[:, 1] + r) / 16))
+    assert bool(inside.all())

@@ -10,7 +10,7 @@ import os
 import pytest
 import torch
 
-from _scenes import (both_sides_order_independent, check_pixels, check_rows, REL_TOL, assert_close, assert_close_groups, sh_band_groups, fp64_envelope, assert_equal_int, cotangents, gsplat_inputs,
+from _scenes import (assert_binning_properties, both_sides_order_independent, oracle_threads, check_pixels, check_rows, REL_TOL, assert_close, assert_close_groups, sh_band_groups, fp64_envelope, assert_equal_int, cotangents, gsplat_inputs,
                      keep_mask, rel_err, to_leaf, zero_borderline, render_bounds, flip_bound_linear, flip_bound_alpha, flip_bound_ratio,
                      flip_bound_unit)
 
@@ -1430,9 +1430,7 @@ def test_against_golden_fixture(dns):
 FULL = {"c2": (1_000_000, 1920, 1080), "c3": (3_000_000, 1600, 1200), "c5": (5_000_000, 1600, 1200)}
 
 
-def _oracle_threads():
-    # the oracle's gradient scatter uses omp atomics: beyond ~32 threads it only gets slower (bench.py cpu_baseline)
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
+_oracle_threads = oracle_threads
 
 
 @pytest.fixture(scope="module", params=sorted(FULL))
@@ -1578,38 +1576,8 @@ def test_full_size_projection_and_binning_match_oracle(dns, orc, workload):
 
 
 def test_full_size_binning_properties(dns, full_scene):
-    from dn_splatter_amd import _ops
-
     gp, cam, m, out = full_scene
-    info = m.last_info
-    assert _ops.binning_status(info["_binning"], info["radii"].numel()) == 0, "a look-back wait of the tile sort timed out"
-    n = info["n_isects"]
-    tiles = info["tiles_bin"][0].long()          # the count the binning walked (== tiles_per_gauss unless tight tile boxes)
-    assert int(tiles.sum()) == n, "sum(tiles_bin) != n_isects"
-    if info.get("tight_tiles"):     # a visible Gaussian may reach alpha >= 1/255 at no pixel centre at all
-        assert int(((tiles > 0) & ~(info["radii"][0] > 0)).sum()) == 0
-    else:
-        assert int(((info["radii"][0] > 0) != (tiles > 0)).sum()) == 0
-    offs = info["isect_offsets"].reshape(-1).long()
-    assert int(offs[0]) == 0 and bool((offs[1:] >= offs[:-1]).all()) and int(offs[-1]) <= n
-    # every tile list is depth-sorted, ties broken by Gaussian index (stable sort, Appendix A.3)
-    fid = info["flatten_ids"].long()
-    d = info["depths"][0][fid]
-    tile_of = torch.searchsorted(offs, torch.arange(n, device=DEV), right=True) - 1
-    same = tile_of[1:] == tile_of[:-1]
-    ok = (d[1:] > d[:-1]) | ((d[1:] == d[:-1]) & (fid[1:] > fid[:-1]))
-    assert bool((ok | ~same).all()), "a tile list is not (depth, index)-sorted"
-    # each Gaussian appears exactly tiles_per_gauss times
-    cnt = torch.bincount(fid, minlength=tiles.shape[0])
-    assert torch.equal(cnt, tiles)
-    # and only in tiles of its bounding box (A.3)
-    xy = info["means2d"][0][fid]
-    r = info["radii"][0][fid].float()
-    tw = info["tile_width"]
-    tx, ty = (tile_of % tw).float(), (tile_of // tw).float()
-    inside = (tx >= torch.floor((xy[:, 0] - r) / 16)) & (tx < torch.ceil((xy[:, 0] + r) / 16)) & \
-             (ty >= torch.floor((xy[:, 1] - r) / 16)) & (ty < torch.ceil((xy[:, 1] + r) / 16))
-    assert bool(inside.all())
+    assert_binning_properties(m.last_info)
 
 
 def test_full_size_image_properties_and_linearity(dns, full_scene):

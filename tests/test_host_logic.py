@@ -345,6 +345,41 @@ int main() {
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
 
 
+def test_fp32_reciprocal_row_division_of_the_pair_generator_is_exact():
+    """csrc/binning.hip gen_pair / gen_pairs: with g.exact (tile columns <= 256 and <= 65536 tiles in the batch) the box row of
+    pair t of a record is floor((t + 0.5f) * (1.f / bw)) in float32 instead of t / bw.  Exhaustively for every bw <= 256 and
+    t < 65536 — with the correctly rounded reciprocal and with it moved one ulp either way, since nothing here depends on the
+    device's reciprocal being correctly rounded.  Then, beyond the range g.exact admits, the first t where it breaks for a few
+    box widths: the margin the switch keeps."""
+    np = pytest.importorskip("numpy")
+    t = np.arange(1 << 16, dtype=np.int64)
+    tf = t.astype(np.float32) + np.float32(0.5)
+
+    def recips(bw):
+        r = np.float32(1.0) / np.float32(bw)
+        return {"-1 ulp": np.nextafter(r, np.float32(0.0)), "rounded": r, "+1 ulp": np.nextafter(r, np.float32(np.inf))}
+
+    for bw in range(1, 257):
+        want = t // bw
+        for name, r in recips(bw).items():
+            row = np.floor(tf * r).astype(np.int64)        # float32 product, then the truncation of the uint conversion
+            bad = np.nonzero(row != want)[0]
+            assert bad.size == 0, f"bw {bw}, reciprocal {name}: t = {int(bad[0])} gives row {int(row[bad[0]])}, not {int(want[bad[0]])}"
+    # the margin: first failing t below 2^22 (none of these widths fails before 2^21)
+    tl = np.arange(1 << 22, dtype=np.int64)
+    tlf = tl.astype(np.float32) + np.float32(0.5)
+    first = []
+    for bw in (3, 7, 100, 255, 256):
+        for name, r in recips(bw).items():
+            bad = np.nonzero(np.floor(tlf * r).astype(np.int64) != tl // bw)[0]
+            if bad.size:
+                first.append((int(bad[0]), bw, name))
+    first.sort()
+    print(f"[host] fp32 reciprocal row division: exact for t < 65536, bw <= 256; first failure below 2^22: "
+          f"t = {first[0][0]}, bw = {first[0][1]} ({first[0][2]} reciprocal)" if first else "none below 2^22")
+    assert not first or first[0][0] >= 1 << 20, first[:3]
+
+
 def test_lazy_info_copies_force_their_lazy_entries(dns):
     """ADVICE r04: ``info`` of the fused path is a dict subclass whose isect_ids / flatten_ids / n_isects are computed on first read;
     dict(info), {**info}, info.copy() and pickling must hand out the computed values, not the placeholder."""
