@@ -474,6 +474,298 @@ def raster_level_scene(orc, seed, N=10_000, W=256, H=256, focal=160.0, D=4, anis
                 borderline=border.bool(), gen=g)
 
 
+# ---- raster-level scenes with an exact list structure (tests/test_gpu_raster_edges.py, tests/test_edge_scenes.py) ---------------
+# Every contributing splat is a point of sigma EDGE_SIGMA centred (within EDGE_JITTER) on ONE pixel centre: alpha there is its opacity
+# (x 0.965 at least), at every other pixel centre below 0.5 / 255.  So each list entry reaches exactly one pixel of one half tile, and
+# a recipe fixes, entry by entry, which pixel blends it, which pixel saturates where and how many entries a half tile keeps.
+EDGE_COUNTS = (0, 1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, 143, 159, 160, 161, 191, 192, 193, 255, 256,
+               257, 383, 384, 385)
+# never: no pixel saturates.  early: one pixel saturates at list index 4, most pixels blend nothing after batch 0 and two pixels
+# walk to the end.  boundary: pixels saturate at indices 64, 128, 256, 384 (their last blended entry ends a batch / a bucket).
+# allstop: every pixel that blends anything saturates, about 3/4 down the list; the entries after that reach only stopped pixels,
+# so the backward's bound `hi` lies inside the list and the entries above it are kept but never walked.
+EDGE_STOPS = ("never", "early", "boundary", "allstop")
+EDGE_OFFSETS = (0, 1, 63)         # range_start mod 64 of the tiles under test (padding entries in the tile in front of each)
+EDGE_SIGMA = 0.27
+EDGE_JITTER = 0.05
+LOW_OPACITY = (0.0055, 0.009)     # low-alpha runs: alpha 1.35/255 .. 2.3/255 at the splat's own pixel, below 0.01/255 anywhere else
+STACK_OPACITY = 0.95              # three of them leave T <= 5.7e-4, the fourth would take T below 4.7e-5: the pixel stops there
+CAP_OPACITY = 0.9999              # 0.003 px off its pixel centre: o vis = 0.9998 > 0.999, alpha clamped: T = 1e-3, then 1e-6 (stop)
+CAP_OFFSET = 0.003                # (not 0: sigma = 0 exactly would sit on the "skip if sigma < 0" decision)
+CULL_OPACITY = 0.002              # listed but culled: below 1/255 at every point
+EDGE_BOUNDARY_STOPS = (64, 128, 256, 384)
+
+
+def edge_pixel(k):
+    """A spread walk over the 128 pixels (16 x 8, row-major) of a half tile."""
+    return (k * 37) % 128
+
+
+def _low(i):
+    lo, hi = LOW_OPACITY
+    return lo + (hi - lo) * ((i * 0.6180339887) % 1.0)
+
+
+def allstop_groups(n):
+    """``allstop``: the first 4 x (this) entries are stacks of four on distinct pixels."""
+    return max(1, (3 * n // 4) // 4)
+
+
+def half_recipe(n, stop, cap=False):
+    """The ``n`` contributing entries of one half tile in list order: [(pixel 0..127, opacity, capped)]."""
+    stack = CAP_OPACITY if cap else STACK_OPACITY
+    if stop == "never" or (stop == "early" and n < 5) or (stop == "allstop" and n < 8):
+        return [(edge_pixel(i), _low(i), False) for i in range(n)]
+    out = []
+    if stop == "early":
+        q, tail = 5, (77, 121)
+        for i in range(n):
+            if 1 <= i <= 4:
+                out.append((q, stack, cap))
+            elif i < 64:
+                p = edge_pixel(i)
+                out.append((p if p != q else q + 1, _low(i), False))
+            else:
+                out.append((tail[i % 2], _low(i), False))
+        return out
+    if stop == "boundary":
+        stops = {s: 3 + 9 * (s // 64) for s in EDGE_BOUNDARY_STOPS if s < n}
+        pix = set(stops.values())
+        for i in range(n):
+            s = next((s for s in stops if s - 3 <= i <= s), None)
+            if s is not None:
+                out.append((stops[s], stack, cap))
+            else:
+                p = edge_pixel(i)
+                out.append((p if p not in pix else (p + 64) % 128, _low(i), False))
+        return out
+    if stop == "allstop":
+        k = 4 * allstop_groups(n)
+        return [(edge_pixel(i // 4), stack, cap) if i < k else (edge_pixel(0), _low(i), False) for i in range(n)]
+    raise ValueError(stop)
+
+
+def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=False, seed=0, pad_to=None):
+    """Raster-level scene (the inputs of rasterize_to_pixels, CPU tensors) from ``cases`` = [(tile, half, n, stop)], one case per tile.
+    Ids: the case entries first (in case order, then list order), then the culled entries ``interleave`` puts in front of every
+    second case entry, then the padding; ``pad_to`` appends invisible splats (radius 0) up to that many records.
+    ``phase``: the list of case k starts at range_start mod 64 = EDGE_OFFSETS[(k + phase) % 3] (padding entries at the end of the
+    tile in front of it, which holds no case).  ``end_align``: the last tile of the frame holds a case, and its list ends on a
+    multiple of 64.  Depths are distinct integers in recipe order.  Channels: ``colors8`` / ``background8``, 8 of them in [0.1, 0.9]
+    (a D-channel render takes the first D)."""
+    tw, th = (W + 15) // 16, (H + 15) // 16
+    T = tw * th
+    cases = sorted(cases)
+    case_tiles = [c[0] for c in cases]
+    assert len(set(case_tiles)) == len(case_tiles), "one case per tile"
+    assert all(1 <= t < T and t - 1 not in case_tiles for t in case_tiles), "the tile in front of a case holds its padding"
+    g = torch.Generator().manual_seed(seed)
+    stride = 2 * max([c[2] for c in cases] + [1]) + 2 * 64 + 8
+    assert (T + 1) * stride < 2 ** 24, "depths must stay exact in float32"
+    rows = []              # (x, y, conic a, b, c, opacity, radius, depth, kind) kind: 0 case, 1 interleaved culled, 2 padding
+    a_pt = 1.0 / EDGE_SIGMA ** 2
+    for t, h, n, stop in cases:
+        x0, y0 = 16 * (t % tw), 16 * (t // tw) + 8 * h
+        jit = torch.rand(max(n, 1), 3, generator=g) * 2 - 1
+        for i, (p, o, centred) in enumerate(half_recipe(n, stop, cap)):
+            dx, dy = (CAP_OFFSET, CAP_OFFSET) if centred else (EDGE_JITTER * float(jit[i, 0]), EDGE_JITTER * float(jit[i, 1]))
+            rows.append((x0 + p % 16 + 0.5 + dx, y0 + p // 16 + 0.5 + dy, a_pt, 0.0 if centred else 0.3 * float(jit[i, 2]), a_pt, o, 1,
+                         1.0 + t * stride + 2 * i + 2, 0))
+    if interleave:
+        for t, h, n, stop in cases:
+            x0, y0 = 16 * (t % tw), 16 * (t // tw)
+            for i in range(0, n, 2):
+                rows.append((x0 + 8.0, y0 + 8.0, 4.0, 0.0, 4.0, CULL_OPACITY, 1, 1.0 + t * stride + 2 * i + 1, 1))
+
+    def boxes(x, y, r):
+        """gsplat's tile box (A.3) of centres x, y and radii r, clipped to the grid"""
+        x, y, r = (torch.as_tensor(v, dtype=torch.float32) for v in (x, y, r))
+        bx0 = torch.clamp(torch.floor((x - r) / 16), 0, tw).long()
+        bx1 = torch.clamp(torch.ceil((x + r) / 16), 0, tw).long()
+        by0 = torch.clamp(torch.floor((y - r) / 16), 0, th).long()
+        by1 = torch.clamp(torch.ceil((y + r) / 16), 0, th).long()
+        return bx0, bx1, by0, by1
+
+    # list lengths without the padding (neighbours' entries whose box reaches a tile are in its list too)
+    base = [0] * T
+    if rows:
+        bx0, bx1, by0, by1 = boxes([r[0] for r in rows], [r[1] for r in rows], [float(r[6]) for r in rows])
+        for i in range(len(rows)):
+            for ty in range(int(by0[i]), int(by1[i])):
+                for tx in range(int(bx0[i]), int(bx1[i])):
+                    base[ty * tw + tx] += 1
+    target = {t: EDGE_OFFSETS[(k + phase) % len(EDGE_OFFSETS)] for k, t in enumerate(case_tiles)}
+    if end_align:
+        assert case_tiles[-1] == T - 1
+        target[T - 1] = (-base[T - 1]) % 64
+    fill = [0] * T
+    start = 0
+    for t in range(T):
+        if t + 1 in target:
+            fill[t] = (target[t + 1] - (start + base[t])) % 64
+        start += base[t] + fill[t]
+    for t in range(T):
+        x0, y0 = 16 * (t % tw), 16 * (t // tw)
+        for j in range(fill[t]):
+            rows.append((x0 + 8.0, y0 + 8.0, 4.0, 0.0, 4.0, CULL_OPACITY, 1, 1.0 + t * stride + stride - 72 + j, 2))
+    R = torch.tensor([r[:6] for r in rows], dtype=torch.float64).reshape(-1, 6)
+    radii = torch.tensor([r[6] for r in rows], dtype=torch.int32)
+    depths = torch.tensor([r[7] for r in rows], dtype=torch.float32)
+    kind = torch.tensor([r[8] for r in rows], dtype=torch.int8)
+    if pad_to is not None:
+        extra = pad_to - R.shape[0]
+        assert extra >= 0
+        R = torch.cat([R, torch.tensor([[8.0, 8.0, 4.0, 0.0, 4.0, CULL_OPACITY]], dtype=torch.float64).repeat(extra, 1)])
+        radii = torch.cat([radii, torch.zeros(extra, dtype=torch.int32)])
+        depths = torch.cat([depths, torch.ones(extra)])
+        kind = torch.cat([kind, torch.full((extra,), 3, dtype=torch.int8)])
+    N = R.shape[0]
+    xys, conics, opac = R[:, 0:2].float().contiguous(), R[:, 2:5].float().contiguous(), R[:, 5].float().contiguous()
+    bx0, bx1, by0, by1 = boxes(xys[:, 0], xys[:, 1], radii.float())
+    tiles = torch.where(radii > 0, (bx1 - bx0) * (by1 - by0), torch.zeros_like(bx0)).to(torch.int32)
+    gc = torch.Generator().manual_seed(1000 + seed)
+    cols = 0.1 + 0.8 * torch.rand(N, 8, generator=gc)
+    bg = 0.1 + 0.8 * torch.rand(8, generator=gc)
+    return dict(W=W, H=H, N=N, xys=xys, conics=conics, opacities=opac, colors8=cols, background8=bg, radii=radii, depths=depths,
+                tiles=tiles, kind=kind, n_case=int((kind == 0).sum()), cases=cases, target=target, fill=fill, tw=tw, th=th, phase=phase,
+                interleave=interleave, cap=cap)
+
+
+def edge_main_cases():
+    """Every count x every stop pattern, one per half tile: 124 cases on tiles 1, 3, ..., 247 of a 256 x 256 frame (16 x 16 tiles)."""
+    cases = []
+    for ci, n in enumerate(EDGE_COUNTS):
+        for si, stop in enumerate(EDGE_STOPS):
+            k = len(cases)
+            cases.append((2 * k + 1, (ci + si) % 2, n, stop))
+    return cases
+
+
+_PARTIAL = [(1, 0, 65, "early"), (5, 1, 129, "allstop"), (9, 1, 97, "never"), (11, 0, 161, "boundary")]
+# name: (W, H, cases, edge_frame options).  height40 / height44: the bottom half tiles of the last tile row lie outside the image /
+# half inside it (tile 9's bottom half carries a case in both).  deep: one list of 20 000+ low-alpha entries.  cap: opacities above
+# the 0.999 cap on every stack.
+EDGE_SMALL = {
+    "height40": (64, 40, _PARTIAL, {}),
+    "height44": (64, 44, _PARTIAL, {}),
+    "deep": (32, 32, [(3, 1, 20001, "never")], {}),
+    "cap": (128, 128, [(2 * k + 1, k % 2, n, st) for k, (n, st) in
+                       enumerate([(n, st) for n in (17, 65, 129, 161, 257) for st in ("early", "boundary", "allstop")])], {"cap": True}),
+}
+# a batch of three cameras (128 x 128), a different recipe in each; every camera's lists end on a multiple of 64, the last tile's
+# with a case in it
+EDGE_CAMERAS = [
+    [(1, 0, 129, "never"), (5, 1, 33, "early"), (9, 0, 161, "boundary"), (63, 1, 65, "allstop")],
+    [(3, 1, 97, "allstop"), (13, 0, 257, "never"), (63, 0, 31, "boundary")],
+    [(7, 0, 193, "early"), (21, 1, 160, "never"), (63, 1, 64, "never")],
+]
+
+
+def edge_cameras(**kw):
+    """The three frames of EDGE_CAMERAS with the same number of records (invisible padding)."""
+    n = max(edge_frame(c, 128, 128, end_align=True, seed=7 + i, **kw)["N"] for i, c in enumerate(EDGE_CAMERAS))
+    return [edge_frame(c, 128, 128, end_align=True, seed=7 + i, pad_to=n, **kw) for i, c in enumerate(EDGE_CAMERAS)]
+
+
+def edge_lists(orc, s):
+    """The reference binning of an edge frame: (offsets [th, tw] int32, flatten_ids int32), the oracle's (gsplat's) lists."""
+    t, ids, fid = orc.isect_tiles(s["xys"], s["radii"], s["depths"], 16, s["tw"], s["th"])
+    assert torch.equal(t, s["tiles"]), "tiles per Gaussian differ from the frame's box count"
+    return orc.isect_offset_encode(ids, s["tw"], s["th"]), fid
+
+
+def edge_model(s, offs, fid):
+    """What the compositing kernels do on each half tile of ``s``, recomputed in float64 from the lists (offs, fid): one dict per
+    (non-empty tile, half) with rs / re (list range), kept (entries with alpha >= 1/255 at some pixel centre of the half: what the
+    rectangle test keeps), contrib (those reaching an in-image pixel), stop {pixel: list index (relative) of the entry that stops it},
+    hi (the backward's walk bound, relative; -1: no work), queue (kept entries up to hi), the bucket sequence with keep masks (takes /
+    carries _masks: 64-entry batches aligned to the list start) and without (_scan: 64 entries down from hi) and the fold of the last
+    bucket in the default mode.  Asserts that no alpha lies within 30 % of 1/255 and no transmittance within 20 % of 1e-4."""
+    W, H, tw, th = s["W"], s["H"], s["tw"], s["th"]
+    T = tw * th
+    offs = offs.reshape(-1).long()
+    xy, cn, op = s["xys"].double(), s["conics"].double(), s["opacities"].double()
+    amin, tmin = 1.0 / 255.0, 1e-4
+    out = []
+    for t in range(T):
+        rs = int(offs[t])
+        re = int(offs[t + 1]) if t + 1 < T else fid.numel()
+        if re <= rs:
+            continue
+        ids = fid[rs:re].long()
+        L = re - rs
+        for h in (0, 1):
+            px = (16 * (t % tw) + torch.arange(16, dtype=torch.float64) + 0.5).repeat(8)
+            py = (16 * (t // tw) + 8 * h + torch.arange(8, dtype=torch.float64) + 0.5).repeat_interleave(16)
+            inimg = (px < W) & (py < H)
+            dx = px[None, :] - xy[ids, 0:1]
+            dy = py[None, :] - xy[ids, 1:2]
+            sig = 0.5 * (cn[ids, 0:1] * dx * dx + cn[ids, 2:3] * dy * dy) + cn[ids, 1:2] * dx * dy
+            al = torch.clamp(op[ids, None] * torch.exp(-sig), max=0.999)
+            assert not bool(((al > 0.7 * amin) & (al < 1.3 * amin)).any()), f"tile {t} half {h}: an alpha within 30 % of 1/255"
+            valid = (sig >= 0) & (al >= amin)
+            kept = valid.any(1)
+            vin = valid & inimg[None, :]
+            lg = torch.where(vin, torch.log1p(-al), torch.zeros_like(al))
+            t_after = torch.exp(torch.cumsum(lg, 0))
+            hit = vin & (t_after <= tmin)
+            stop = {}
+            bin_final = torch.full((128,), -1, dtype=torch.long)
+            for p in torch.nonzero(vin.any(0)).reshape(-1).tolist():
+                hs = torch.nonzero(hit[:, p]).reshape(-1)
+                st = int(hs[0]) if hs.numel() else L
+                tv = t_after[:st + 1, p][vin[:st + 1, p]]
+                assert not bool(((tv > tmin / 1.2) & (tv < tmin * 1.2)).any()), f"tile {t} half {h} pixel {p}: T within 20 % of 1e-4"
+                blend = torch.nonzero(vin[:st, p]).reshape(-1)
+                if st < L:
+                    assert blend.numel(), f"tile {t} half {h} pixel {p} stops at its first entry"
+                    stop[p] = st
+                    bin_final[p] = rs + st - 1                   # the forward's last_ids: the entry before the one that stops it
+                elif blend.numel():
+                    bin_final[p] = min(rs + (int(blend[-1]) // 64) * 64 + 64, re) - 1    # else the end of its last batch with a blend
+            hi = min(int(bin_final.max()), re - 1)
+            q = kept & (torch.arange(L) <= hi - rs) if hi >= rs else torch.zeros(L, dtype=torch.bool)
+
+            def buckets(masks):
+                qn, takes, carries = 0, [], []
+                if hi < rs:
+                    return takes, carries
+                batch, cursor = (hi - rs) >> 6, hi
+                while True:
+                    while qn < 128 and (batch >= 0 if masks else cursor >= rs):
+                        if masks:
+                            qn += int(q[64 * batch:64 * batch + 64].sum())
+                            batch -= 1
+                        else:
+                            qn += int(q[max(rs, cursor - 63) - rs:cursor - rs + 1].sum())
+                            cursor -= 64
+                    take = min(qn, 128)
+                    qn -= take
+                    takes.append(take)
+                    carries.append(qn)
+                    if take == 0:
+                        return takes, carries
+            tm, cm = buckets(True)
+            ts, cs = buckets(False)
+            last = ([x for x in tm if x > 0] or [0])[-1]
+            out.append(dict(tile=t, half=h, rs=rs, re=re, L=L, kept=int(kept.sum()), contrib=int(vin.any(1).sum()), stop=stop,
+                            hi=(hi - rs) if hi >= rs else -1, queue=int(q.sum()), takes_masks=tm, carries_masks=cm, takes_scan=ts,
+                            carries_scan=cs, fold=4 if 0 < last <= 32 else 2 if 0 < last <= 64 else 1, n_stopped=len(stop),
+                            n_blending=int((bin_final >= 0).sum()), kept_above_hi=int(kept[max(hi - rs + 1, 0):].sum())))
+    return out
+
+
+def regime_line(r, what=""):
+    """One printed line per half tile: the regime the kernels reach on it (edge_model)."""
+    tm = r["takes_masks"][:-1]
+    st = sorted(set(r["stop"].values()))
+    return (f"[raster] {what}tile {r['tile']} {('top', 'bottom')[r['half']]}: list {r['L']} at range_start % 64 = {r['rs'] % 64}, "
+            f"kept {r['kept']} (in the image {r['contrib']}), {r['n_stopped']} of {r['n_blending']} blending pixels stop"
+            f"{' at ' + str(st[:4]) if st else ''}, hi {r['hi']}, queue {r['queue']} (+{r['kept_above_hi']} kept above hi), buckets "
+            f"{tm if len(tm) <= 5 else tm[:2] + ['...'] + tm[-2:]}, fold {r['fold']}, carried max {max(r['carries_masks'] or [0])} "
+            f"(masks) / {max(r['carries_scan'] or [0])} (scan)")
+
+
 HULL_KEYS = ("means2d", "absgrad", "conics", "colors", "opacities")
 
 
