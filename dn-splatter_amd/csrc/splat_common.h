@@ -86,48 +86,16 @@ __device__ __forceinline__ void dns_snug_tile_bbox(float mx, float my, float ca,
     y0 = max(y0, (int)fy0); y1 = max(min(y1, (int)fy1), y0);
 }
 
-// XCD-aware block remap (guide §5.5 T1): hardware places block b on XCD b % 8.  Give every XCD one
-// contiguous band of work ids so that neighbouring tiles — which share most of their splats —
-// hit the same 4 MiB L2.  Bijective for any grid size.
-__device__ __forceinline__ int dns_xcd_remap(int b, int n)
-{
-    const int nx = 8;
-    int q = n / nx, r = n % nx;
-    int xcd = b % nx, k = b / nx;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + k;
-}
-
-// blockIdx -> tile for the compositing kernels.  Measured on the 1080p / 1 M benchmark frame (raster_bwd, ms):
-//   0  one band of consecutive tile rows per XCD (dns_xcd_remap: neighbouring tiles share an L2)      1.89
-//   1  identity: consecutive tiles round-robin over the XCDs                                           1.87
-//   2  bands over a row-interleaved image (every XCD gets rows from the whole height)                  1.91
+// blockIdx -> tile for the compositing kernels: the identity.  Hardware places block b on XCD b % 8; measured on the 1080p / 1 M
+// benchmark frame (raster_bwd, ms; the other two orders: docs/history.md, section 13):
+//   one contiguous band of tile rows per XCD (neighbouring tiles share a 4 MiB L2)                     1.89
+//   identity: consecutive tiles round-robin over the XCDs                                              1.87
+//   bands over a row-interleaved image (every XCD gets rows from the whole height)                     1.91
 // Both kernels are bound by vector instructions, not by L2 misses (0.2 TB/s of HBM traffic), so the L2 locality of the
 // bands buys nothing here and the finer interleave of the identity order balances the XCDs slightly better.
-#ifndef DNS_TILE_ORDER
-#define DNS_TILE_ORDER 1
-#endif
 __device__ __forceinline__ int dns_tile_of_block(int b, int n_tiles, int tw)
 {
-#if DNS_TILE_ORDER == 0
-    return dns_xcd_remap(b, n_tiles);
-#elif DNS_TILE_ORDER == 1
     return b;
-#else
-    const int w = dns_xcd_remap(b, n_tiles);
-    const int th = n_tiles / tw;
-    int rp = w / tw;
-    const int col = w - rp * tw;
-    int row = rp;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int cnt = (th - c + 7) >> 3;      // image rows with row % 8 == c
-        if (rp >= 0 && rp < cnt) row = c + 8 * rp;
-        rp -= cnt;                              // negative once the class is found: no later class matches
-        if (rp < 0) rp = -0x40000000;
-    }
-    return row * tw + col;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -141,36 +109,28 @@ __device__ __forceinline__ int dns_tile_of_block(int b, int n_tiles, int tw)
 // cannot make the two kernels round differently.
 #define DNS_LOG2E 1.4426950408889634f
 
-// DNS_EXP_SYM = 1: the quadratic form is evaluated through its two half-gradients,
+// The quadratic form is evaluated through its two half-gradients,
 //     u = na dx + hb dy,  w = hb dx + nc dy,  e = dx u + dy w        (na, hb, nc = -log2e/2 * (a, b, c)),
 // which are exactly what the backward needs for d sigma / d(dx, dy) = -(2 / log2e) (u, w): the mean gradient costs one
 // multiply per component instead of rebuilding a dx + b dy from the unscaled conic (3 packed instructions less per
 // step, and the unscaled conic leaves the backward's registers).  The forward shares na dx and hb dx between the two
-// pixels of a lane, so it pays nothing for the sixth operation.  DNS_EXP_SYM = 0 keeps the 5-operation Horner form.
-#ifndef DNS_EXP_SYM
-#define DNS_EXP_SYM 1
-#endif
+// pixels of a lane, so it pays nothing for the sixth operation.
 
 struct DnsConicE {
-    float na, nb, nc;  // -log2e/2 * a, [SYM: -log2e/2 * b (= hb) | else: -log2e * b], -log2e/2 * c
+    float na, nb, nc;  // -log2e/2 * (a, b, c); nb is the hb of the formulas above
 };
 
 __device__ __forceinline__ DnsConicE dns_conic_e(float ca, float cb, float cc)
 {
     DnsConicE q;
     q.na = (-0.5f * DNS_LOG2E) * ca;
-#if DNS_EXP_SYM
     q.nb = (-0.5f * DNS_LOG2E) * cb;
-#else
-    q.nb = (-DNS_LOG2E) * cb;
-#endif
     q.nc = (-0.5f * DNS_LOG2E) * cc;
     return q;
 }
 
 // e = -log2e * sigma  (<= 0 for a valid pair).  The operation sequence below is THE definition both compositing kernels
 // follow instruction for instruction (the backward in packed form), so that they take bit-identical skip decisions.
-#if DNS_EXP_SYM
 __device__ __forceinline__ float dns_half_grad_u(const DnsConicE &q, float dx, float dy) { return __builtin_fmaf(q.nb, dy, q.na * dx); }
 __device__ __forceinline__ float dns_half_grad_w(const DnsConicE &q, float dx, float dy) { return __builtin_fmaf(q.nc, dy, q.nb * dx); }
 __device__ __forceinline__ float dns_exponent(const DnsConicE &q, float dx, float dy)
@@ -178,13 +138,6 @@ __device__ __forceinline__ float dns_exponent(const DnsConicE &q, float dx, floa
     const float u = dns_half_grad_u(q, dx, dy), w = dns_half_grad_w(q, dx, dy);
     return __builtin_fmaf(dx, u, dy * w);
 }
-#else
-__device__ __forceinline__ float dns_exponent(const DnsConicE &q, float dx, float dy)
-{
-    const float u = __builtin_fmaf(q.na, dx, q.nb * dy);
-    return __builtin_fmaf(dx, u, (q.nc * dy) * dy);
-}
-#endif
 
 __device__ __forceinline__ float dns_exp2(float e) { return __builtin_amdgcn_exp2f(e); }
 

@@ -388,7 +388,7 @@ def test_render_modes(dns, orc, render_mode):
 def test_direct_colors_and_background(dns, orc, n_colors):
     """sh_degree=None path (dn_model.py:491-493) with a background, 5 or 7 feature channels + depth.  7 + depth = 8 channels is the
     record's capacity: the compositing backward then has no free cotangent slot for the next pixel's x and takes the column from
-    its pixel counter instead (DNS_BWD_PX_SLOT needs D < 8) — the one instantiation no other test reaches."""
+    its pixel counter instead (the free eighth cotangent slot needs D < 8) — the one instantiation no other test reaches."""
     inp, viewmat, K, _ = gsplat_inputs(3000, 96, 80, focal=70.0, seed=7, anisotropic=True)
     g_ = torch.Generator().manual_seed(9)
     inp["colors"] = torch.rand(3000, n_colors, generator=g_)

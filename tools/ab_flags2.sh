@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # A/B of a -D flag applied to BOTH compositing kernels (raster_fwd + raster_bwd) inside one gpurun call.
-#   /usr/local/graft/bin/gpurun --timeout 900 -- 'bash tools/ab_flags2.sh "-DDNS_TILE_ORDER=0" "-DDNS_TILE_ORDER=2"'
+#   bash tools/ab_flags2.sh "-DDNS_FWD_WAVES_PER_EU=0 -DDNS_BWD_WAVES_PER_EU=4" "-DDNS_FWD_WAVES_PER_EU=7 -DDNS_BWD_WAVES_PER_EU=3"
 cd "${GRAFT_REPO_ROOT:-.}"
 C=dn-splatter_amd/csrc
 COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"

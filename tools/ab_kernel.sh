@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
 # A/B timing of build variants of ONE kernel file inside a single gpurun call (box-to-box variation is ~2 %).
-#   /usr/local/graft/bin/gpurun --timeout 900 -- 'bash tools/ab_kernel.sh raster_fwd "-DDNS_FWD_PX=2" "-DDNS_FWD_PX=4"'
+#   bash tools/ab_kernel.sh raster_fwd "-DDNS_FWD_PACKED=0" "-DDNS_FWD_PACKED=1"
+# An experiment that has no switch is timed as another version of the whole source file: tools/ab_files.sh.
 # The first variant is run again at the end; the library is left built with it.
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out

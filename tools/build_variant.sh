@@ -1,9 +1,9 @@
 #!/usr/bin/env bash
 # Cross-compiles a VARIANT of libdnsplat.so (extra -D flags) into gpurun_ab/lib_<name>.so, here in the CPU container;
 # gpurun_ab/ travels with the snapshot, so a GPU call only has to time the libraries (tools/ab_libs.sh).
-#   tools/build_variant.sh base ""            tools/build_variant.sh sym "-DDNS_EXP_SYM=1"
+#   tools/build_variant.sh base ""            tools/build_variant.sh packed "-DDNS_FWD_PACKED=1"
 # <FILE>_SRC=path (BINNING_SRC, PROJECT_SRC, RASTER_FWD_SRC, RASTER_BWD_SRC) compiles another version of that one source file
-# (e.g. `git show <rev>:dn-splatter_amd/csrc/binning.hip > /tmp/b.hip`) in place of the tree's — for changes that have no switch.
+# (e.g. `git show <rev>:dn-splatter_amd/csrc/binning.hip > /tmp/b.hip`) in place of the tree's — how a change that has no switch is A/B-tested.
 set -euo pipefail
 NAME=$1; FLAGS=${2:-}
 cd "$(dirname "$0")/../dn-splatter_amd/csrc"
