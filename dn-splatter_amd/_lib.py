@@ -139,6 +139,10 @@ class ProjGrads(ctypes.Structure):
     ]
 
 
+class PoseGrads(ctypes.Structure):
+    _fields_ = [("partials", c_void_p), ("v_viewmat", c_void_p), ("c2w", c_void_p), ("v_c2w", c_void_p)]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -150,6 +154,8 @@ EXPORTS = [
     "dnsplat_densify_split", "dnsplat_dn_loss", "dnsplat_ssim", "dnsplat_edge_aware_logl1", "dnsplat_tv_loss", "dnsplat_scale_reg", "dnsplat_sh_grads_from_factors", "dnsplat_sh_factors",
     "dnsplat_project_bwd", "dnsplat_sh_grads_add_factors", "dnsplat_packed_slab_floats", "dnsplat_visible_index",
     "dnsplat_sh_grads_from_packed",
+    # added after ABI 15 (additive, found by symbol): the camera pose gradient
+    "dnsplat_pose_partial_rows", "dnsplat_project_bwd_pose",
 ]
 
 _lib = None
@@ -219,9 +225,13 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_visible_index.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.dnsplat_sh_grads_from_packed.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float,
                                                    c_void_p, c_int32, c_void_p, c_int32, c_void_p]
+        L.dnsplat_pose_partial_rows.restype = c_size_t
+        L.dnsplat_pose_partial_rows.argtypes = [c_int32]
+        L.dnsplat_project_bwd_pose.argtypes = [ctypes.POINTER(Scene), ctypes.POINTER(Camera), ctypes.POINTER(ProjOut),
+                                               ctypes.POINTER(ProjGrads), ctypes.POINTER(PoseGrads), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
-                            "dnsplat_packed_slab_floats"):
+                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

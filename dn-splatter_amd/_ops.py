@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BinArgs, Camera, DnPost, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BinArgs, Camera, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -371,6 +371,7 @@ class _ProjectFn(torch.autograd.Function):
         # one launch per camera of the batch (C = 1 in training, dn_model.py:421; C > 1 for the batched render loops of the
         # offline consumers): per-camera outputs are the rows of [C,N,...] tensors, the records of camera c are rows
         # c*N .. (c+1)*N of one [C*N,16] buffer — the layout dnsplat_bin_* / dnsplat_raster_* take for a batch
+        ctx.viewmat_shape = viewmat.shape
         viewmat = viewmat.reshape(-1, 4, 4)
         K = K.reshape(-1, 3, 3)
         C = viewmat.shape[0]
@@ -460,6 +461,11 @@ class _ProjectFn(torch.autograd.Function):
         v_cmp = v_comp.reshape(C, N).contiguous() if (v_comp is not None and cfg.antialiased) else None
         sh_K = ctx.sh_K
         need = ctx.needs_input_grad
+        # the camera pose (gsplat's viewmats.grad; the pose a camera optimiser trains): one [4,4] per camera from the pose twin of the
+        # kernel, never summed over cameras and never all-reduced.  Not asked for: exactly the plain launch.
+        v_viewmat = torch.empty(C, 4, 4, dtype=torch.float32, device=dev) if need[8] else None
+        pose_rows = (torch.empty(_lib.lib().dnsplat_pose_partial_rows(N), 16, dtype=torch.float32, device=dev)
+                     if v_viewmat is not None else None)
         total = None      # running sum over the cameras of a batch (C > 1); a single camera writes its outputs directly
 
         for c in range(C):
@@ -506,6 +512,10 @@ class _ProjectFn(torch.autograd.Function):
             # rebuilds into), one camera per rank.  With the concatenated gsplat layout the coefficient gradient is an
             # intermediate autograd tensor that nobody could fill in afterwards, so the kernel writes the rows itself.
             if ex is not None and ctx.layout == "split" and sh_K == 16 and C == 1 and getattr(ex, "slices", 1) > 1:
+                if v_viewmat is not None:
+                    raise _lib.DnsplatError("a camera pose gradient (viewmats / camera_to_world that requires grad) is not supported "
+                                            "together with dp.SlicedShExchange: its launches cover slices of the Gaussians; use "
+                                            "dp.ShFactorExchange or freeze the pose")
                 # dp.SlicedShExchange: the same entry point on K slices of the Gaussians (every row pointer advanced by g0, N = n_k),
                 # each with its own mini slab.  Under capture (record_only) nothing is launched here: the argument structs stay with
                 # the exchange, graph.GraphedDpStep issues launch k + all-gather k behind each replay; the geometry gradients are
@@ -582,8 +592,14 @@ class _ProjectFn(torch.autograd.Function):
                 # the rows land in the flat bucket, whose zero rows are tracked: a Gaussian that is culled again is not re-zeroed
                 g.sh_zero_state = _ptr(GRAD_ARENA.sh_state)
                 g.zero_state_geometry = int(all(GRAD_ARENA.holds(t) for t in (v_means, v_quats, v_scales, v_opac)))
-            _lib.run("dnsplat_project_bwd", _lib.lib().dnsplat_project_bwd, ctypes.byref(scene), ctypes.byref(cam), ctypes.byref(fwd),
-                     ctypes.byref(g), _stream())
+            if v_viewmat is not None:
+                pg = PoseGrads()
+                pg.partials, pg.v_viewmat = _ptr(pose_rows), _ptr(v_viewmat[c])
+                _lib.run("dnsplat_project_bwd_pose", _lib.lib().dnsplat_project_bwd_pose, ctypes.byref(scene), ctypes.byref(cam),
+                         ctypes.byref(fwd), ctypes.byref(g), ctypes.byref(pg), _stream())
+            else:
+                _lib.run("dnsplat_project_bwd", _lib.lib().dnsplat_project_bwd, ctypes.byref(scene), ctypes.byref(cam), ctypes.byref(fwd),
+                         ctypes.byref(g), _stream())
             outs = [v_means, v_quats, v_scales, v_opac, v_coeffs, v_sh0, v_shN, v_colors]
             if total is None:
                 total = outs
@@ -591,7 +607,8 @@ class _ProjectFn(torch.autograd.Function):
                 for acc, t in zip(total, outs):
                     if acc is not None:
                         acc.add_(t)
-        return tuple(t if (t is not None and need[i]) else None for i, t in enumerate(total)) + (None, None, None, None, None, None)
+        return tuple(t if (t is not None and need[i]) else None for i, t in enumerate(total)) + (
+            None if v_viewmat is None else v_viewmat.reshape(ctx.viewmat_shape), None, None, None, None, None)
 
 
 def project(means, quats, scales, opacities, *, coeffs=None, sh0=None, shN=None, colors=None, viewmat, K,
@@ -1174,11 +1191,16 @@ def camera_prepare(c2w: Tensor, fx: float, fy: float, cx: float, cy: float, with
     ``c2w`` [3,4] (or [1,3,4]) on the GPU -> viewmat[4,4], K[3,3], normal_frame[12] | None
     (+ with_flag: a zeroed int32 [1] device word, the frame's opacity-saturation flag for project(..., saturation_flag=);
     n_depth_max > 0: the flag is followed by that many zeroed floats, the per-camera depth maxima of the fused epilogue —
-    ``flag.depth_max`` — so that the frame needs no fill launch for either)."""
+    ``flag.depth_max`` — so that the frame needs no fill launch for either).
+    A ``c2w`` that requires grad (a camera optimiser's pose) makes ``viewmat`` an autograd function of it; K and the normal frame
+    carry no gradient."""
     c2w = _f32c(c2w.reshape(-1)[:12], "camera_to_worlds")
     dev = c2w.device
     out = torch.empty(16 + 9 + 12, dtype=torch.float32, device=dev)
     viewmat, K, nf = out[:16], out[16:25], out[25:37]
+    pose_leaf = c2w.requires_grad and torch.is_grad_enabled()
+    if pose_leaf:
+        viewmat = torch.empty(16, dtype=torch.float32, device=dev)      # an autograd output of its own, not a view of `out`
     # the words the launch zeroes live in their own buffer: autograd saves viewmat / K, and a later in-place fill of depth_max
     # (a re-run after a capacity overflow) must not touch their version counter
     zeros = torch.empty(1 + n_depth_max, dtype=torch.float32, device=dev) if with_flag else None
@@ -1189,8 +1211,31 @@ def camera_prepare(c2w: Tensor, fx: float, fy: float, cx: float, cy: float, with
         DEPTH_MAX_OF[flag.data_ptr()] = zeros[1:1 + n_depth_max]
         while len(DEPTH_MAX_OF) > 16:          # prepared cameras nobody rendered (an exception in between): oldest first
             DEPTH_MAX_OF.pop(next(iter(DEPTH_MAX_OF)))
+    if pose_leaf:
+        viewmat = _ViewmatOfC2wFn.apply(c2w, viewmat)
     res = (viewmat.view(4, 4), K.view(3, 3), (nf if with_normal_frame else None))
     return res + (flag,) if with_flag else res
+
+
+class _ViewmatOfC2wFn(torch.autograd.Function):
+    """Makes the view matrix dnsplat_camera_prepare wrote an autograd function of the pose it was made from (a camera optimiser's
+    output): the backward is the chain through nerfstudio's get_viewmat (columns 1, 2 negated, transpose, -R^T T) on twelve
+    numbers.  K and the normal frame carry no gradient: the reference takes them from the raw camera (dn_model.py:476, 551, 560)."""
+
+    @staticmethod
+    def forward(ctx, c2w, viewmat):
+        ctx.save_for_backward(c2w)
+        return viewmat.view(16)
+
+    @staticmethod
+    def backward(ctx, v_viewmat):
+        (c2w,) = ctx.saved_tensors
+        c = c2w.view(3, 4)
+        vV = v_viewmat.reshape(4, 4)
+        R = torch.cat([c[:, :1], -c[:, 1:3]], 1)                       # get_viewmat's flipped rotation, rows k
+        g = vV[:3, :3].t() - c[:, 3:4] * vV[:3, 3][None, :]            # viewmat[r][k] = R[k][r], viewmat[r][3] = -sum_k R[k][r] T[k]
+        v_T = -(R @ vV[:3, 3])
+        return torch.cat([g[:, :1], -g[:, 1:3], v_T[:, None]], 1).reshape(12), None
 
 
 # zeroed depth_max words that came with a saturation flag (keyed by the flag's address; taken once by _RasterDnFn.forward)

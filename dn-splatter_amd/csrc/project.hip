@@ -744,6 +744,12 @@ struct BwdParams {
     dnsplat_proj_out o;
     dnsplat_proj_grads g;
 };
+struct BwdPoseParams : BwdParams {
+    float *pose_rows;      // dnsplat_pose_grads.partials
+};
+template <bool POSE> struct BwdParamsSel { using type = BwdParams; };
+template <> struct BwdParamsSel<true> { using type = BwdPoseParams; };
+template <bool POSE> using BwdParamsT = typename BwdParamsSel<POSE>::type;
 
 // 169 VGPRs as hipcc allocates them freely = 2 waves / SIMD, one register over the 168 that allow 3: pinned to 3 (no scratch;
 // DNS_PROJ_BWD_WAVES=0 lets the compiler choose).
@@ -751,14 +757,29 @@ struct BwdParams {
 #define DNS_PROJ_BWD_WAVES 3
 #endif
 #if DNS_PROJ_BWD_WAVES
-#define DNS_PROJ_BWD_OCC __attribute__((amdgpu_waves_per_eu(DNS_PROJ_BWD_WAVES, DNS_PROJ_BWD_WAVES)))
+#define DNS_PROJ_BWD_OCC_T(POSE) __attribute__((amdgpu_waves_per_eu((POSE) ? 2 : DNS_PROJ_BWD_WAVES, DNS_PROJ_BWD_WAVES)))
 #else
-#define DNS_PROJ_BWD_OCC
+#define DNS_PROJ_BWD_OCC_T(POSE)
 #endif
-template <int L>
-__global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC void project_bwd_kernel(BwdParams p)
+// POSE: the twin behind dnsplat_project_bwd_pose.  Besides everything below it reduces the view-matrix gradient of the workgroup's
+// Gaussians into one row of 16 floats, pose_rows[blockIdx.x] = { v_Rv (9, row-major) | v_t (3) | G (3) | 0 }:
+//   v_t  = sum v_mc                       mean_c  = Rv mean + t
+//   v_Rv = sum v_mc (x) mean + (v_Cc + v_Cc^T) Rv Sigma         covar_c = Rv Sigma Rv^T, Sigma = M M^T
+//   G    = sum d loss / d (camera centre) through the SH view direction mean - centre
+// One lane holds one Gaussian, so the lane's 15 values are summed over the wave with a butterfly of cross-lane moves (every lane
+// ends with the same sum, in an order fixed by the lane numbers: bit-reproducible), and lane 0 stores the row.  A culled lane adds
+// zeros.  No atomics, no LDS beside the coefficient rows.  pose_reduce_kernel / pose_finalize_kernel sum the rows in fp64.
+// Every addition sits behind `if constexpr (POSE)`: the POSE = false instantiations are the kernels they were (same registers, 3 waves
+// per SIMD).  The twin's 15 sums and three extra 3x3 products do not fit 168 registers without scratch: it runs at 2 waves / SIMD.
+template <int L, bool POSE = false>
+__global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC_T(POSE) void project_bwd_kernel(BwdParamsT<POSE> p)
 {
     __shared__ float sh_lds[L == SH_DIRECT ? 1 : SH_STAGE_THREADS * ShRowTraits<L>::LDS_ROW];
+    float pose[POSE ? 15 : 1];
+    if constexpr (POSE) {
+#pragma unroll
+        for (int i = 0; i < 15; ++i) pose[i] = 0.f;
+    }
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int g0 = blockIdx.x * SH_STAGE_THREADS;
     const int nG = min(SH_STAGE_THREADS, p.s.N - g0);
@@ -959,6 +980,11 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC void project_bwd
                 v_mean[0] += (vdn[0] - dot * dx) * inorm;
                 v_mean[1] += (vdn[1] - dot * dy) * inorm;
                 v_mean[2] += (vdn[2] - dot * dz) * inorm;
+                if constexpr (POSE) {      // direction = mean - centre: the centre receives minus what the mean receives
+                    pose[12] = -((vdn[0] - dot * dx) * inorm);
+                    pose[13] = -((vdn[1] - dot * dy) * inorm);
+                    pose[14] = -((vdn[2] - dot * dz) * inorm);
+                }
             }
             ch = 3;
         } else {
@@ -1060,6 +1086,22 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC void project_bwd
         const float *Rv = cam.Rv;
 #pragma unroll
         for (int i = 0; i < 3; ++i) v_mean[i] += Rv[0 + i] * v_mc[0] + Rv[3 + i] * v_mc[1] + Rv[6 + i] * v_mc[2];
+        if constexpr (POSE) {
+            float S[9], SR[9], SRM[9], SRS[9];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) S[3 * i + j] = v_Cc[3 * i + j] + v_Cc[3 * j + i];
+            mm3(S, Rv, SR);
+            mm3(SR, st.M, SRM);
+            mm3_abt(SRM, st.M, SRS);          // (v_Cc + v_Cc^T) Rv M M^T
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) pose[3 * i + j] = v_mc[i] * mean[j] + SRS[3 * i + j];
+                pose[9 + i] = v_mc[i];
+            }
+        }
         float tmp[9], v_cov[9];
         mm3_atb(Rv, v_Cc, tmp);
         mm3(tmp, Rv, v_cov);
@@ -1118,6 +1160,20 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC void project_bwd
         }
     }
     }  // g < N
+    if constexpr (POSE) {
+        static_assert(SH_STAGE_THREADS == DNS_WAVE, "one wave per workgroup: the row is the wave's sum");
+#pragma unroll
+        for (int i = 0; i < 15; ++i)
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) pose[i] += __shfl_xor(pose[i], off, DNS_WAVE);
+        if (threadIdx.x == 0) {
+            dns_v4f *row = reinterpret_cast<dns_v4f *>(p.pose_rows + (size_t)blockIdx.x * 16);
+            row[0] = dns_v4f{pose[0], pose[1], pose[2], pose[3]};
+            row[1] = dns_v4f{pose[4], pose[5], pose[6], pose[7]};
+            row[2] = dns_v4f{pose[8], pose[9], pose[10], pose[11]};
+            row[3] = dns_v4f{pose[12], pose[13], pose[14], 0.f};
+        }
+    }
     if (L != SH_DIRECT && !p.g.sh_grads_skip) {
         __syncthreads();
         float *base = (L == SH_CAT ? p.g.v_sh0 : p.g.v_shN) + (size_t)g0 * ShRowTraits<L>::ROW;
@@ -1128,6 +1184,81 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC void project_bwd
     }
     // what memory holds now: zero rows exactly where the Gaussian is culled (lanes beyond N: bits unused)
     if (track_zero && threadIdx.x == 0) p.g.sh_zero_state[blockIdx.x] = ~vis_rows;
+}
+
+// Level 1 of the fixed-order sum of the pose rows: workgroup b adds rows [256 b, 256 b + 256) in fp64 — thread (s, j) the rows
+// s, s + 16, ... of column j, then the sixteen s in order — and writes one row of 16 doubles.
+constexpr int POSE_CHUNK = 256;
+__global__ __launch_bounds__(256) void pose_reduce_kernel(int n_rows, const float *__restrict__ rows, double *__restrict__ sums)
+{
+    __shared__ double part[256];
+    const int j = threadIdx.x & 15, s = threadIdx.x >> 4;
+    const int r0 = blockIdx.x * POSE_CHUNK, r1 = min(n_rows, r0 + POSE_CHUNK);
+    double acc = 0.0;
+    for (int r = r0 + s; r < r1; r += 16) acc += (double)rows[(size_t)r * 16 + j];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double t = 0.0;
+        for (int k = 0; k < 16; ++k) t += part[16 * k + threadIdx.x];
+        sums[(size_t)blockIdx.x * 16 + threadIdx.x] = t;
+    }
+}
+
+// Level 2 (one workgroup): the chunk sums in order, then the view-matrix gradient.  The camera centre reaches the colours as
+// inverse(viewmat)[:3, 3] (gsplat), and the derivative of a general inverse is -V^-T (d/dV^-1) V^-T: with c the centre and G its
+// gradient, v_Rv -= (Rv G) (x) c, v_t -= Rv G, bottom row = -(c . G) [c, 1].  v_c2w: the chain through camera_prepare_kernel
+// (nerfstudio get_viewmat: columns 1, 2 negated, transpose, -R^T T); the bottom row does not enter it.
+__global__ __launch_bounds__(256) void pose_finalize_kernel(int n_chunks, const double *__restrict__ sums, const float *__restrict__ viewmat,
+                                                            const float *__restrict__ c2w, float *__restrict__ v_viewmat,
+                                                            float *__restrict__ v_c2w)
+{
+    __shared__ double part[256];
+    __shared__ double tot[16];
+    const int j = threadIdx.x & 15, s = threadIdx.x >> 4;
+    double acc = 0.0;
+    for (int r = s; r < n_chunks; r += 16) acc += sums[(size_t)r * 16 + j];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double t = 0.0;
+        for (int k = 0; k < 16; ++k) t += part[16 * k + threadIdx.x];
+        tot[threadIdx.x] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double Rv[9], t[3], c[3], RG[3], vV[16];
+    for (int i = 0; i < 3; ++i) {
+        for (int k = 0; k < 3; ++k) Rv[3 * i + k] = (double)viewmat[4 * i + k];
+        t[i] = (double)viewmat[4 * i + 3];
+    }
+    const double *G = tot + 12;
+    for (int i = 0; i < 3; ++i) {
+        c[i] = -(Rv[0 + i] * t[0] + Rv[3 + i] * t[1] + Rv[6 + i] * t[2]);
+        RG[i] = Rv[3 * i + 0] * G[0] + Rv[3 * i + 1] * G[1] + Rv[3 * i + 2] * G[2];
+    }
+    const double cG = c[0] * G[0] + c[1] * G[1] + c[2] * G[2];
+    for (int i = 0; i < 3; ++i) {
+        for (int k = 0; k < 3; ++k) vV[4 * i + k] = tot[3 * i + k] - RG[i] * c[k];
+        vV[4 * i + 3] = tot[9 + i] - RG[i];
+        vV[12 + i] = -cG * c[i];
+    }
+    vV[15] = -cG;
+    for (int i = 0; i < 16; ++i) v_viewmat[i] = (float)vV[i];
+    if (c2w && v_c2w) {
+        // viewmat[r][k] = R[k][r], viewmat[r][3] = -sum_k R[k][r] T[k] with R[k] = (c2w[k][0], -c2w[k][1], -c2w[k][2]), T[k] = c2w[k][3]
+        for (int k = 0; k < 3; ++k) {
+            const double T = (double)c2w[4 * k + 3];
+            double vT = 0.0;
+            for (int r = 0; r < 3; ++r) {
+                const double Rkr = (r == 0 ? 1.0 : -1.0) * (double)c2w[4 * k + r];
+                const double vR = vV[4 * r + k] - T * vV[4 * r + 3];
+                v_c2w[4 * k + r] = (float)((r == 0 ? 1.0 : -1.0) * vR);
+                vT -= Rkr * vV[4 * r + 3];
+            }
+            v_c2w[4 * k + 3] = (float)vT;
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void pack_splats_kernel(int N, const float *__restrict__ means2d,
@@ -1405,6 +1536,50 @@ extern "C" int dnsplat_project_bwd(const dnsplat_scene *scene, const dnsplat_cam
         case SH_CAT: hipLaunchKernelGGL(project_bwd_kernel<SH_CAT>, grid, block, 0, (hipStream_t)stream, p); break;
         default: hipLaunchKernelGGL(project_bwd_kernel<SH_DIRECT>, grid, block, 0, (hipStream_t)stream, p);
     }
+    DNS_CHECK_LAUNCH();
+    return DNSPLAT_OK;
+}
+
+// rows of 16 floats: one per workgroup of the projection backward, then one row of 16 doubles (= 2 float rows) per POSE_CHUNK of them
+extern "C" size_t dnsplat_pose_partial_rows(int32_t N)
+{
+    if (N <= 0) return 0;
+    const size_t nb = ((size_t)N + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS;
+    return nb + 2 * ((nb + POSE_CHUNK - 1) / POSE_CHUNK);
+}
+
+extern "C" int dnsplat_project_bwd_pose(const dnsplat_scene *scene, const dnsplat_camera *cam, const dnsplat_proj_out *fwd,
+                                        const dnsplat_proj_grads *grads, const dnsplat_pose_grads *pose, dnsplat_stream_t stream)
+{
+    if (!scene || !cam || !fwd || !grads || !pose) return DNSPLAT_ERR_INVALID_ARG;
+    if (scene->N < 0 || !pose->v_viewmat || !cam->viewmat || (pose->c2w == nullptr) != (pose->v_c2w == nullptr)) return DNSPLAT_ERR_INVALID_ARG;
+    if (scene->N > 0 && (!pose->partials || ((uintptr_t)pose->partials & 15) != 0)) return DNSPLAT_ERR_INVALID_ARG;
+    const int nb = (scene->N + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS;
+    const int n_chunks = (nb + POSE_CHUNK - 1) / POSE_CHUNK;
+    double *sums = reinterpret_cast<double *>(pose->partials + (size_t)nb * 16);
+    if (scene->N > 0) {
+        if (!grads->radii || !grads->v_splats || !grads->v_means || !grads->v_quats || !grads->v_scales || !grads->v_opacities ||
+            !cam->K)
+            return DNSPLAT_ERR_INVALID_ARG;
+        if (scene->sh_degree > 3) return DNSPLAT_ERR_UNSUPPORTED;
+        if (fwd->with_normal_channels && !cam->normal_frame) return DNSPLAT_ERR_INVALID_ARG;
+        BwdPoseParams p;
+        p.s = *scene; p.c = *cam; p.o = *fwd; p.g = *grads; p.pose_rows = pose->partials;
+        dim3 block(SH_STAGE_THREADS), grid(nb);
+        int layout = sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride);
+        if (layout != SH_DIRECT && layout != sh_layout(scene, grads->v_sh0, grads->v_sh0_stride, grads->v_shN, grads->v_shN_stride))
+            layout = SH_DIRECT;
+        switch (layout) {
+            case SH_SPLIT: hipLaunchKernelGGL((project_bwd_kernel<SH_SPLIT, true>), grid, block, 0, (hipStream_t)stream, p); break;
+            case SH_CAT: hipLaunchKernelGGL((project_bwd_kernel<SH_CAT, true>), grid, block, 0, (hipStream_t)stream, p); break;
+            default: hipLaunchKernelGGL((project_bwd_kernel<SH_DIRECT, true>), grid, block, 0, (hipStream_t)stream, p);
+        }
+        DNS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(pose_reduce_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, nb, pose->partials, sums);
+        DNS_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(pose_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_chunks, sums, cam->viewmat, pose->c2w,
+                       pose->v_viewmat, pose->v_c2w);
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
 }

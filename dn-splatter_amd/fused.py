@@ -101,13 +101,21 @@ def render_dn_outputs(
     fx: float, fy: float, cx: float, cy: float, width: int, height: int, sh_degree: int, background_rgb: Tensor,
     near_plane: float = 0.01, far_plane: float = 1e10, eps2d: float = 0.3, absgrad: bool = True,
     pair_counters: Optional[Tensor] = None, sigmoid_colors: bool = False,
+    normal_camera_to_world: Optional[Tensor] = None,
 ) -> Tuple[Dict[str, Tensor], Dict]:
     """The whole replaced part of ``get_outputs`` (classic mode, predict_normals=True) in six launches:
     camera prepare, fused projection, binning, compositing with the dn-splatter epilogue, depth fill +
     depth->normal stencil; backward = compositing backward (taking the image cotangents directly) + fused
     projection backward.  Returns ``(outputs, info)`` with the output keys of dn_model.py:605-612 minus
-    ``background``."""
+    ``background``.
+
+    ``camera_to_world`` is the pose the scene is projected with (dn_model.py:475: the camera optimiser's output); if it
+    requires grad it receives its gradient.  ``normal_camera_to_world`` (default: the same tensor) is the pose the normal flip
+    and the camera-frame rotation of the normals use — the reference takes the RAW ``camera.camera_to_worlds`` there
+    (dn_model.py:551, 560); it carries no gradient."""
     viewmat, K, nf, flag = _ops.camera_prepare(camera_to_world, fx, fy, cx, cy, with_flag=True, n_depth_max=1)
+    if normal_camera_to_world is not None and normal_camera_to_world is not camera_to_world:
+        nf = _ops.camera_prepare(normal_camera_to_world.detach(), fx, fy, cx, cy)[2]
     outs, info = _render_dn_batch(means, quats, scales, opacities, features_dc, features_rest, viewmat[None], K[None], nf[None],
                                   [(fx, fy, cx, cy)], width, height, sh_degree, background_rgb, near_plane, far_plane, eps2d,
                                   absgrad, pair_counters, flag, sigmoid_colors=sigmoid_colors)

@@ -25,6 +25,9 @@ Usage::
         optimizer.step()
     step.check()                                    # raises if any replayed frame overflowed its intersection buffers
 
+A trained camera pose (a camera optimiser's output, ``get_outputs(cam, optimized_camera_to_world=pose)``) is one more entry of
+``params``: its ``.grad`` is reset before the capture and lands in the same tensor at every replay, like the Gaussians' gradients.
+
 ``copies=2`` captures the step twice (two graphs, two sets of buffers; gradients still land in the same ``GradArena``)
 and alternates between them: while one copy runs, the host can read what the other one left behind — bench.py uses it
 to read the HIP-event brackets of every replay without ever making the GPU wait for the host.

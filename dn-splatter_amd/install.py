@@ -79,10 +79,15 @@ def fused_get_outputs(self, camera) -> Dict[str, torch.Tensor]:
     sigmoid_colors = not (cfg.sh_degree > 0)                           # dn_model.py:486-493
     sh_degree = min(self.step // cfg.sh_degree_interval, cfg.sh_degree) if cfg.sh_degree > 0 else 0
     c2w = optimized_camera_to_world.reshape(-1, 3, 4)[0]
+    # the projection takes the optimised pose (dn_model.py:475), which receives its gradient; the normal flip and the camera-frame
+    # rotation of the normals take the raw one (dn_model.py:551, 560).  With the optimiser off the two are the same tensor
+    raw_c2w = camera.camera_to_worlds
+    raw_c2w = None if raw_c2w is optimized_camera_to_world else raw_c2w.reshape(-1, 3, 4)[0]
     if cfg.predict_normals:
         out, info = _fused.render_dn_outputs(
             p["means"], p["quats"], p["scales"], p["opacities"], p["features_dc"], p["features_rest"], c2w, fx, fy, cx, cy, W, H,
-            sh_degree=sh_degree, background_rgb=background.to(c2w.device), absgrad=True, sigmoid_colors=sigmoid_colors)
+            sh_degree=sh_degree, background_rgb=background.to(c2w.device), absgrad=True, sigmoid_colors=sigmoid_colors,
+            normal_camera_to_world=raw_c2w)
         if crop_ids is None:
             self.gauss_params["normals"] = info["normals_world"]       # dn_model.py:558
     else:

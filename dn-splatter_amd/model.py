@@ -179,12 +179,16 @@ class DNSplatterRenderer:
         c = self.config
         return min(self.step // c.sh_degree_interval, c.sh_degree)
 
-    def get_outputs(self, camera: Camera) -> Dict[str, Tensor]:
+    def get_outputs(self, camera: Camera, optimized_camera_to_world: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """``optimized_camera_to_world`` [1,3,4]: what ``camera_optimizer.apply_to_camera(camera)`` returned (dn_model.py:422) — the
+        pose the scene is projected with, which receives a gradient if it requires one.  The normal flip and the camera-frame
+        rotation of the normals keep the raw ``camera.camera_to_worlds`` (dn_model.py:551, 560).  Default: the raw pose for both."""
         gp = self.gauss_params
         cfg = self.config
         if cfg.rasterize_mode not in ["antialiased", "classic"]:
             raise ValueError("Unknown rasterize_mode: %s", cfg.rasterize_mode)
         c2w = camera.camera_to_worlds
+        pose = c2w if optimized_camera_to_world is None else optimized_camera_to_world.reshape(-1, 3, 4)
         W, H = int(camera.width), int(camera.height)
         background = self._background(c2w.device)
 
@@ -196,9 +200,9 @@ class DNSplatterRenderer:
             # everything between the parameters and the output dict in HIP; config.sh_degree == 0
             # (dn_model.py:486-493: sigmoid(colours), no SH) is the same pass with the sigmoid inside the projection kernels
             out, info = _fused.render_dn_outputs(
-                means, quats, scales, opacities, features_dc, features_rest, c2w[0], float(camera.fx), float(camera.fy),
+                means, quats, scales, opacities, features_dc, features_rest, pose[0], float(camera.fx), float(camera.fy),
                 float(camera.cx), float(camera.cy), W, H, sh_degree=self._sh_degree_to_use(), background_rgb=background,
-                absgrad=True, sigmoid_colors=(cfg.sh_degree == 0))
+                absgrad=True, sigmoid_colors=(cfg.sh_degree == 0), normal_camera_to_world=None if pose is c2w else c2w[0])
             gp["normals"] = info["normals_world"]          # dn_model.py:558
             if self.training and info["means2d"].requires_grad:
                 info["means2d"].retain_grad()              # dn_model.py:517-518
@@ -211,7 +215,7 @@ class DNSplatterRenderer:
             out["background"] = background
             return out
 
-        viewmat = get_viewmat(c2w)                       # dn_model.py:475
+        viewmat = get_viewmat(pose)                      # dn_model.py:475
         K = camera.get_intrinsics_matrices().to(c2w.device)   # dn_model.py:476
         if self.fused and cfg.sh_degree > 0 and not (cfg.rasterize_mode == "antialiased" and cfg.predict_normals):
             render, alpha, normals_im, info = _fused.render_dn(

@@ -50,7 +50,10 @@ extern "C" {
  * gradient rows of persistently culled Gaussians are not re-zeroed), dnsplat_sh_grads_add_factors, the packed (visible rows only)
  * colour-gradient slabs: dnsplat_visible_index, dnsplat_proj_grads.sh_packed, dnsplat_sh_grads_from_packed; 15 = dnsplat_ssim (the
  * SSIM term alone, for a loss stack that otherwise stays in PyTorch), dnsplat_proj_grads.zero_state_geometry (zero gradient rows of
- * culled Gaussians skipped per workgroup), dnsplat_edge_aware_logl1, dnsplat_tv_loss. */
+ * culled Gaussians skipped per workgroup), dnsplat_edge_aware_logl1, dnsplat_tv_loss.
+ * Entry points added after 15 are purely additive — new symbols and new structs, no existing struct or call changes — and are found
+ * by symbol: the version stays 15 and the binding refuses a library that lacks one (dnsplat_pose_partial_rows,
+ * dnsplat_project_bwd_pose / dnsplat_pose_grads: the camera pose gradient). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -520,6 +523,26 @@ typedef struct dnsplat_proj_grads {
 int dnsplat_project_bwd(const dnsplat_scene *scene, const dnsplat_camera *cam,
                         const dnsplat_proj_out *fwd, const dnsplat_proj_grads *grads,
                         dnsplat_stream_t stream);
+
+/* Camera pose gradient (added after ABI 15, found by symbol).  dnsplat_project_bwd_pose does everything dnsplat_project_bwd does —
+ * same dnsplat_proj_grads semantics, the parameter gradients come out bit-equal — and ALSO reduces the gradient of the loss with
+ * respect to camera.viewmat, which gsplat's rasterization() returns as viewmats.grad and a camera optimiser trains the pose with
+ * (dn_model.py:114-116, 475).  Every workgroup of 64 Gaussians sums its share in registers (no atomics) into one row of
+ * `partials`; two small launches add the rows in a fixed order in fp64.  The result is bit-reproducible for equal inputs, with
+ * or without dnsplat_raster_args.det_partials.  Three launches, no allocation, no synchronisation. */
+typedef struct dnsplat_pose_grads {
+    float *partials;       /* workspace: dnsplat_pose_partial_rows(N) rows of 16 floats, 16-byte aligned; contents need not survive */
+    float *v_viewmat;      /* out, device [16] row-major 4x4.  Rows 0-2: rotation block and translation column.  Row 3: the camera
+                              centre enters the SH view direction as inverse(viewmat)[:3,3] (gsplat), whose derivative reaches the
+                              bottom row too: -(c . G) [c_x, c_y, c_z, 1], c the centre, G its gradient; zero without SH colours */
+    const float *c2w;      /* optional device [12]: the nerfstudio camera-to-world rows dnsplat_camera_prepare made viewmat from */
+    float *v_c2w;          /* optional device [12] (both or neither): v_viewmat chained through dnsplat_camera_prepare's viewmat
+                              (column flip, transpose, -R^T T); the normal frame and K carry no gradient */
+} dnsplat_pose_grads;
+
+size_t dnsplat_pose_partial_rows(int32_t N);   /* >= ceil(N / 64), monotone in N */
+int dnsplat_project_bwd_pose(const dnsplat_scene *scene, const dnsplat_camera *cam, const dnsplat_proj_out *fwd,
+                             const dnsplat_proj_grads *grads, const dnsplat_pose_grads *pose, dnsplat_stream_t stream);
 
 #ifdef __cplusplus
 }
