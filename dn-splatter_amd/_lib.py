@@ -156,6 +156,8 @@ EXPORTS = [
     "dnsplat_sh_grads_from_packed",
     # added after ABI 15 (additive, found by symbol): the camera pose gradient
     "dnsplat_pose_partial_rows", "dnsplat_project_bwd_pose",
+    # likewise: the Pearson depth losses
+    "dnsplat_pearson_scratch_bytes", "dnsplat_pearson_depth",
 ]
 
 _lib = None
@@ -229,9 +231,13 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_pose_partial_rows.argtypes = [c_int32]
         L.dnsplat_project_bwd_pose.argtypes = [ctypes.POINTER(Scene), ctypes.POINTER(Camera), ctypes.POINTER(ProjOut),
                                                ctypes.POINTER(ProjGrads), ctypes.POINTER(PoseGrads), c_void_p]
+        L.dnsplat_pearson_scratch_bytes.restype = c_size_t
+        L.dnsplat_pearson_scratch_bytes.argtypes = [c_int32]
+        L.dnsplat_pearson_depth.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                            c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
-                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows"):
+                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

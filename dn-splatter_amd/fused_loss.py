@@ -180,6 +180,123 @@ class EdgeAwareLogL1(torch.nn.Module):
         return _EdgeAwareLogL1Fn.apply(pred, gt, rgb, mask)
 
 
+class _PearsonFn(torch.autograd.Function):
+    """``w_whole`` x the whole-frame Pearson loss + ``w_box`` x the MEAN of the box losses, value and gradient w.r.t. the prediction in
+    one entry-point call (``dnsplat_pearson_depth``).  ``rows`` / ``cols``: int64 device tensors of box origins, passed on unread."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, mask, rows, cols, box, whole, w_whole, w_box):
+        shape = pred.shape
+        n_boxes = 0 if rows is None else int(rows.numel())
+        if n_boxes:
+            H, W = shape[0], shape[1]
+            if pred.numel() != H * W:
+                raise NotImplementedError(f"dnsplat Pearson boxes take one [H,W] or [H,W,1] depth image, got {tuple(shape)}")
+            if rows.dtype != torch.int64 or cols.dtype != torch.int64 or cols.numel() != n_boxes or rows.device != pred.device \
+                    or cols.device != pred.device:
+                raise ValueError("dnsplat Pearson boxes: rows and cols are int64 tensors of one length on the prediction's device")
+            rows, cols = rows.contiguous(), cols.contiguous()
+        else:
+            H, W = 1, pred.numel()                       # the whole-frame region is a set of pixels: any shape
+            rows = cols = None
+        if gt.numel() != pred.numel():
+            raise ValueError(f"dnsplat Pearson: prediction {tuple(shape)} and ground truth {tuple(gt.shape)} differ in size")
+        p2 = _f32c(pred.reshape(H, W), "pred"); g2 = _f32c(gt.reshape(H, W).float(), "gt")
+        m = None
+        if mask is not None:
+            if mask.dtype != torch.bool or mask.numel() != H * W:
+                raise ValueError("dnsplat Pearson: mask must be a bool tensor of the depth's shape")
+            m = mask.reshape(H, W).contiguous()
+        dev = p2.device
+        need = ctx.needs_input_grad[0]
+        v = torch.empty(H, W, dtype=torch.float32, device=dev) if need else None
+        L = _lib.lib()
+        scratch = torch.empty(L.dnsplat_pearson_scratch_bytes(n_boxes) // 8, dtype=torch.float64, device=dev)
+        sums = torch.empty(2, dtype=torch.float32, device=dev)
+        w_each = w_box / n_boxes if n_boxes else 0.0                      # the division by n_corr stays on this side
+        _lib.run("dnsplat_pearson_depth", L.dnsplat_pearson_depth, W, H, _ptr(p2), _ptr(g2), _ptr(m), 1 if whole else 0, n_boxes,
+                 int(box), _ptr(rows), _ptr(cols), w_whole if whole else 0.0, w_each, _ptr(v), _ptr(scratch), _ptr(sums), _stream())
+        if need:
+            ctx.save_for_backward(v)
+            ctx.shape = shape
+        if whole and n_boxes:
+            return w_whole * sums[0] + w_each * sums[1]
+        return w_whole * sums[0] if whole else w_each * sums[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        (v,) = ctx.saved_tensors
+        return ((v * g).reshape(ctx.shape),) + (None,) * 8
+
+
+def _no_gt_grad(gt: Tensor, what: str) -> None:
+    if gt.requires_grad:
+        raise NotImplementedError(f"dnsplat {what} differentiates the prediction only")
+
+
+def pearson_depth(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+    """``PearsonDepthLoss()(pred, gt)`` (losses.py:428-450) over all pixels of ``pred`` (any shape), or — with a bool ``mask`` of the
+    same shape — ``PearsonDepthLoss()(pred[mask], gt[mask])`` without the gather; gradient w.r.t. ``pred``.  Fewer than two pixels: nan."""
+    _no_gt_grad(gt, "pearson_depth")
+    return _PearsonFn.apply(pred, gt, mask, None, None, 0, True, 1.0, 0.0)
+
+
+def local_pearson_depth(pred: Tensor, gt: Tensor, rows: Tensor, cols: Tensor, box: int = 128) -> Tensor:
+    """The loop of ``LocalPearsonDepthLoss.forward`` (losses.py:480-485) for given origins: the mean over the boxes
+    ``[rows[i] : rows[i] + box, cols[i] : cols[i] + box]`` of the Pearson loss; ``pred`` [H,W] or [H,W,1], ``rows`` / ``cols`` int64 tensors
+    on its device, never read on the host.  No boxes: nan (the reference's 0 / 0) without a launch."""
+    _no_gt_grad(gt, "local_pearson_depth")
+    if rows.numel() == 0:
+        return pred.new_full((), float("nan"), dtype=torch.float32)
+    return _PearsonFn.apply(pred, gt, None, rows, cols, box, False, 0.0, 1.0)
+
+
+def pearson_depth_combined(pred: Tensor, gt: Tensor, rows: Tensor, cols: Tensor, box: int = 128, w_whole: float = 1.0,
+                           w_box: float = 1.0, mask: Optional[Tensor] = None) -> Tensor:
+    """``w_whole * pearson_depth(pred, gt, mask) + w_box * local_pearson_depth(pred, gt, rows, cols, box)`` in one entry-point call
+    (the ``PearsonDepth`` branch of ``DNRegularization.get_depth_loss``: w_box = depth_lambda)."""
+    _no_gt_grad(gt, "pearson_depth_combined")
+    if rows.numel() == 0:
+        return w_whole * pearson_depth(pred, gt, mask) + float("nan")
+    return _PearsonFn.apply(pred, gt, mask, rows, cols, box, True, float(w_whole), float(w_box))
+
+
+def draw_pearson_boxes(depth_pred: Tensor, box_p: int = 128, p_corr: float = 0.5):
+    """The box origins as ``LocalPearsonDepthLoss.forward`` draws them (losses.py:469-476): the same two ``torch.randint`` calls in
+    the same order with the same bounds, on the prediction's device — a seeded run consumes the generator as the reference does."""
+    H, W = depth_pred.shape[0], depth_pred.shape[1]
+    count = int(p_corr * (H // box_p) * (W // box_p))
+    dev = depth_pred.device
+    rows = torch.randint(0, H - box_p, size=(count,), device=dev)        # first draw: top rows, upper bound exclusive
+    cols = torch.randint(0, W - box_p, size=(count,), device=dev)        # second draw: left columns
+    return rows, cols
+
+
+class PearsonDepthLoss(torch.nn.Module):
+    """Drop-in for ``dn_splatter.losses.PearsonDepthLoss`` (losses.py:428-450): ``forward(depth_pred, depth_gt)`` on tensors of any one
+    shape.  Gradient w.r.t. the prediction only.  The reference's ``assert not torch.any(torch.isnan(co))`` is a host synchronisation
+    and is not reproduced: a nan comes back as a nan."""
+
+    def forward(self, depth_pred: Tensor, depth_gt: Tensor) -> Tensor:
+        return pearson_depth(depth_pred, depth_gt)
+
+
+class LocalPearsonDepthLoss(torch.nn.Module):
+    """Drop-in for ``dn_splatter.losses.LocalPearsonDepthLoss`` (losses.py:454-485): ``forward(depth_pred, depth_gt, box_p=128,
+    p_corr=0.5)`` on an [H,W] or [H,W,1] depth image.  The origins are drawn as the reference draws them (``draw_pearson_boxes``) and
+    handed to the kernels as device data: no slice by a device scalar, so no host synchronisation.  ``n_corr == 0`` returns nan (the reference's 0 / 0) without a launch; a frame that is no larger than a box raises
+    what ``torch.randint`` raises.  The per-box ``assert not torch.any(torch.isnan(co))`` of the reference is a host synchronisation
+    and is not reproduced.  Gradient w.r.t. the prediction only."""
+
+    def __init__(self):
+        super().__init__()
+        self.pearson_depth_loss = PearsonDepthLoss()
+
+    def forward(self, depth_pred: Tensor, depth_gt: Tensor, box_p: int = 128, p_corr: float = 0.5) -> Tensor:
+        rows, cols = draw_pearson_boxes(depth_pred, box_p, p_corr)
+        return local_pearson_depth(depth_pred, depth_gt, rows, cols, box_p)
+
+
 class _TVLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred):

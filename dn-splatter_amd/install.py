@@ -147,13 +147,18 @@ def install_losses(model):
     ``DNRegularization`` / ``AGSMeshRegularization`` construct (regularization_strategy.py:131-144): ``strategy.depth_loss.loss``
     (``EdgeAwareLogL1(implementation="scalar")`` -> ``fused_loss.EdgeAwareLogL1``) and ``strategy.normal_smooth_loss.loss``
     (``TVLoss`` -> ``fused_loss.TVLoss``), the strategy's ``get_scale_loss`` method (-> ``fused_loss.scale_reg``); also
-    ``install_ssim(model)``.  Everything else of ``get_loss_dict`` stays the reference's
-    PyTorch code.  Returns the list of what was swapped."""
+    ``install_ssim(model)``.  A ``DNRegularization`` whose ``depth_loss_type`` is ``PearsonDepth`` builds its local term anew on every
+    call (regularization_strategy.py:171), out of reach of a module swap: its ``get_depth_loss`` method is replaced
+    (``_hip_pearson_depth_loss``: both Pearson terms in one ``dnsplat_pearson_depth`` call); a holder whose inner module is a
+    ``PearsonDepthLoss`` / ``LocalPearsonDepthLoss`` gets the drop-in of that name.  Everything else of ``get_loss_dict`` stays the
+    reference's PyTorch code.  Returns the list of what was swapped."""
     from . import fused_loss
 
     swapped = []
     strategy = getattr(model, "regularization_strategy", None)
     for holder_name, cls_name, make in (("depth_loss", "EdgeAwareLogL1", fused_loss.EdgeAwareLogL1),
+                                        ("depth_loss", "PearsonDepthLoss", fused_loss.PearsonDepthLoss),
+                                        ("depth_loss", "LocalPearsonDepthLoss", fused_loss.LocalPearsonDepthLoss),
                                         ("normal_smooth_loss", "TVLoss", fused_loss.TVLoss)):
         holder = getattr(strategy, holder_name, None)
         inner = getattr(holder, "loss", None)
@@ -171,6 +176,21 @@ def install_losses(model):
 
         strategy.get_scale_loss = _hip_scale_loss
         swapped.append("regularization_strategy.get_scale_loss")
+    if strategy is not None and type(strategy).__name__ == "DNRegularization" \
+            and getattr(getattr(strategy, "depth_loss_type", None), "value", None) == "PearsonDepth" \
+            and getattr(strategy.get_depth_loss, "__name__", "") != "_hip_pearson_depth_loss":
+        def _hip_pearson_depth_loss(pred_depth, gt_depth, **kwargs):
+            """regularization_strategy.py:161-186, PearsonDepth branch."""
+            valid_gt_mask = gt_depth > strategy.depth_tolerance
+            # the origins of the local term, drawn as LocalPearsonDepthLoss.forward draws them (losses.py:469-476)
+            rows, cols = fused_loss.draw_pearson_boxes(pred_depth)
+            depth_loss = fused_loss.pearson_depth_combined(pred_depth, gt_depth.float(), rows, cols, 128, 1.0, strategy.depth_lambda)
+            depth_loss = (depth_loss * valid_gt_mask.sum()) / valid_gt_mask.sum()        # :169-170, :173-174 (no valid pixel: nan)
+            depth_loss += strategy.depth_lambda * depth_loss                              # :184
+            return depth_loss
+
+        strategy.get_depth_loss = _hip_pearson_depth_loss
+        swapped.append("regularization_strategy.get_depth_loss")
     if hasattr(model, "ssim"):
         install_ssim(model)
         swapped.append("ssim")

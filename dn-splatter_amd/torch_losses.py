@@ -7,6 +7,7 @@ with the renderer; nothing here is a kernel of ours.  It follows
 * ``DNSplatterModel.get_loss_dict``                      dn_splatter/dn_model.py:614-729
 * ``DNRegularization.get_loss`` / depth / normal / scale dn_splatter/regularization_strategy.py:146-199
 * ``EdgeAwareLogL1``, ``LogL1``, ``L1``, ``TVLoss``      dn_splatter/losses.py:154-224, 279-295
+* ``PearsonDepthLoss``, ``LocalPearsonDepthLoss``        dn_splatter/losses.py:428-485 (depth_loss_type = PearsonDepth)
 * the inherited RGB term of nerfstudio's ``SplatfactoModel.get_loss_dict``: ``(1 - l) * L1 + l * (1 - SSIM)`` with
   ``l = ssim_lambda = 0.2``; ``self.ssim`` is, in dn-splatter, torchmetrics' ``StructuralSimilarityIndexMeasure(data_range=1.0,
   kernel_size=11)`` (dn_model.py:180; nerfstudio itself holds pytorch_msssim's SSIM): an 11 x 11 Gaussian window, sigma 1.5, averaged
@@ -162,6 +163,45 @@ def edge_aware_log_l1(pred: Tensor, gt: Tensor, rgb: Tensor, mask: Optional[Tens
 def tv_loss(pred: Tensor) -> Tensor:
     """TVLoss (losses.py:279-295): mean absolute difference to the right neighbour plus to the lower neighbour."""
     return _dcol(pred).abs().mean() + _drow(pred).abs().mean()
+
+
+def _standardised(x: Tensor) -> Tensor:
+    """x less its mean, over its unbiased standard deviation + 1e-6."""
+    d = x - x.mean()
+    return d / (d.std() + 1e-6)
+
+
+def pearson_depth(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+    """PearsonDepthLoss (losses.py:428-450): 1 - the mean product of the two arguments, each centred on its mean and divided by its
+    unbiased standard deviation + 1e-6.  ``mask``: the loss of ``pred[mask], gt[mask]``, as the other depth branches call it (a
+    boolean-mask gather: a host synchronisation).  The reference's assert on a nan correlation is left out."""
+    if mask is not None:
+        pred, gt = pred[mask], gt[mask]
+    return 1 - (_standardised(pred) * _standardised(gt)).mean()
+
+
+def local_pearson_depth(pred: Tensor, gt: Tensor, rows: Tensor, cols: Tensor, box: int = 128) -> Tensor:
+    """The loop of LocalPearsonDepthLoss (losses.py:480-485) for GIVEN box origins (the reference draws them with two
+    ``torch.randint`` calls, :475-476): the mean over the boxes of ``pearson_depth`` of the box's pixels.  The origins come to the
+    host once (the reference slices with device scalars: four synchronisations per box).  No boxes: 0 / 0 = nan, as the reference."""
+    n = int(rows.numel())
+    loss = torch.zeros((), dtype=pred.dtype, device=pred.device)
+    for r, c in zip(rows.tolist(), cols.tolist()):
+        loss = loss + pearson_depth(pred[r:r + box, c:c + box].reshape(-1), gt[r:r + box, c:c + box].reshape(-1))
+    return loss / n
+
+
+def pearson_depth_term(pred_depth: Tensor, gt_depth: Tensor, rows: Tensor, cols: Tensor, box: int = 128, depth_lambda: float = 0.2,
+                       depth_tolerance: float = 0.1) -> Tensor:
+    """``DNRegularization.get_depth_loss`` for ``depth_loss_type = PearsonDepth`` (regularization_strategy.py:161-186) with the
+    origins of the local term given: both terms times the number of valid ground-truth pixels and divided by it again (nan when
+    there is none), the local one weighted by depth_lambda, and the sum once more ``+= depth_lambda x`` itself."""
+    valid = gt_depth > depth_tolerance
+    whole = (pearson_depth(pred_depth, gt_depth.float()) * valid.sum()) / valid.sum()
+    local = (local_pearson_depth(pred_depth, gt_depth.float(), rows, cols, box) * valid.sum()) / valid.sum()
+    depth_loss = whole + depth_lambda * local
+    depth_loss = depth_loss + depth_lambda * depth_loss
+    return depth_loss
 
 
 def _ssim_hip(pred: Tensor, gt: Tensor) -> Tensor:

@@ -53,7 +53,8 @@ extern "C" {
  * culled Gaussians skipped per workgroup), dnsplat_edge_aware_logl1, dnsplat_tv_loss.
  * Entry points added after 15 are purely additive — new symbols and new structs, no existing struct or call changes — and are found
  * by symbol: the version stays 15 and the binding refuses a library that lacks one (dnsplat_pose_partial_rows,
- * dnsplat_project_bwd_pose / dnsplat_pose_grads: the camera pose gradient). */
+ * dnsplat_project_bwd_pose / dnsplat_pose_grads: the camera pose gradient; dnsplat_pearson_depth / dnsplat_pearson_scratch_bytes: the
+ * Pearson depth losses). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -464,6 +465,37 @@ int dnsplat_edge_aware_logl1(int32_t width, int32_t height, const float *pred, c
                              float *v_x, float *v_y, float *scratch, float *sums, dnsplat_stream_t stream);
 int dnsplat_tv_loss(int32_t width, int32_t height, int32_t channels, const float *pred, float *v_pred, float *scratch, float *sums,
                     dnsplat_stream_t stream);
+
+/* Additive in ABI 15 (found by symbol).  The Pearson depth losses of depth_loss_type = PearsonDepth — losses.py:428-450
+ * (PearsonDepthLoss) on the whole frame and :454-485 (LocalPearsonDepthLoss) on n_boxes windows of box x box pixels, as
+ * regularization_strategy.py:167-177 combines them — value and gradient w.r.t. the prediction in at most five launches, where the
+ * reference loops over the boxes in Python and slices each with device scalars.  Per region: both arguments centred
+ * on their means, divided by the UNBIASED standard deviation + 1e-6, co = mean of the product, loss = 1 - co.
+ *   pred, gt   [H,W] fp32.
+ *   mask       [H,W] bytes (torch.bool) or NULL: only these pixels enter the whole-frame region (depth_loss(pred[mask], gt[mask])
+ *              without the gather); needs whole != 0.  Boxes ignore it.
+ *   whole      non-zero: the whole-frame region takes part.
+ *   box_rows, box_cols   DEVICE int64 [n_boxes] (what torch.randint returns: passed on as drawn, never read on the host): the upper
+ *              left corner of each box, 0 <= row <= H - box, 0 <= col <= W - box (values outside are clamped into that range).  Boxes
+ *              may overlap and repeat; a repeated box counts twice.  Any n_boxes >= 0; any 2 <= box <= min(W, H) (a box of more than
+ *              128 x 128 pixels is read twice instead of being kept in registers).
+ *   sums       out, device [2]: sums[0] = 1 - co of the whole frame (0 without it), sums[1] = sum over the boxes of 1 - co_b (the
+ *              caller divides by the number of boxes).
+ *   v_pred     out [H,W] or NULL (values only): w_whole * d sums[0] / d pred + w_box * d sums[1] / d pred, each term rounded to fp32
+ *              before the two products and the sum (the combined call equals the weighted sum of the two separate calls bit for bit).
+ *   scratch    dnsplat_pearson_scratch_bytes(n_boxes) bytes, 8-byte aligned; contents need not survive.
+ * Second moments are centred (two sweeps, sums in double), every reduction has a fixed order and there is no atomic: the result is
+ * bit-reproducible.  A region of fewer than two pixels gives nan (value and gradient), as the reference's std.  A region whose
+ * prediction is constant has the value 1 - 0, and the gradient autograd gives it: torch's backward of std() passes nothing through a
+ * standard deviation of exactly 0, the path through the numerator remains.  No allocation, no synchronisation.
+ * Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL pred / gt / scratch / sums, width < 1, height < 1, n_boxes < 0, a mask
+ * with whole == 0, and with n_boxes > 0: NULL origins, box < 2, box > min(W, H); DNSPLAT_ERR_UNSUPPORTED for n_boxes > 0 and
+ * box > 46340 (box * box is an int32).  With n_boxes == 0 neither box nor the origins are looked at: the whole-frame call has no box
+ * to name and passes 0. */
+size_t dnsplat_pearson_scratch_bytes(int32_t n_boxes);   /* 0 for n_boxes < 0 */
+int dnsplat_pearson_depth(int32_t width, int32_t height, const float *pred, const float *gt, const uint8_t *mask, int32_t whole,
+                          int32_t n_boxes, int32_t box, const int64_t *box_rows, const int64_t *box_cols, float w_whole, float w_box,
+                          float *v_pred, void *scratch, float *sums, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
