@@ -15,11 +15,12 @@ import torch
 from oracle import dense_ref
 
 
-def project_per_gaussian(means, quats, scales, V, K, W, H, eps2d=0.3, near=0.01, far=1e10, radius_clip=0.0):
-    """dense_ref.project with view matrix V[n] for Gaussian n."""
+def project_per_gaussian(means, quats, scales, V, K, W, H, eps2d=0.3, near=0.01, far=1e10, radius_clip=0.0, rotmats=None):
+    """dense_ref.project with view matrix V[n] for Gaussian n.  ``rotmats`` [n,3,3]: the Gaussians' rotations, given instead of derived
+    from ``quats``."""
     Rv, t = V[:, :3, :3], V[:, :3, 3]
     mean_c = torch.einsum("nij,nj->ni", Rv, means) + t
-    Rq = dense_ref.quat_to_rotmat(quats)
+    Rq = dense_ref.quat_to_rotmat(quats) if rotmats is None else rotmats
     M = Rq * scales[:, None, :]
     covar = M @ M.transpose(1, 2)
     covar_c = Rv @ covar @ Rv.transpose(1, 2)
