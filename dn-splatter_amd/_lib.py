@@ -158,6 +158,8 @@ EXPORTS = [
     "dnsplat_pose_partial_rows", "dnsplat_project_bwd_pose",
     # likewise: the Pearson depth losses
     "dnsplat_pearson_scratch_bytes", "dnsplat_pearson_depth",
+    # likewise: the filtered normal loss of the AGS-Mesh strategy
+    "dnsplat_ags_normal_scratch_bytes", "dnsplat_ags_normal_loss",
 ]
 
 _lib = None
@@ -235,9 +237,12 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_pearson_scratch_bytes.argtypes = [c_int32]
         L.dnsplat_pearson_depth.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                             c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.dnsplat_ags_normal_scratch_bytes.restype = c_size_t
+        L.dnsplat_ags_normal_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_ags_normal_loss.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float] + [c_void_p] * 7
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
-                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes"):
+                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

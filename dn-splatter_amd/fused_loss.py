@@ -354,6 +354,101 @@ def scale_reg(scales: Tensor) -> Tensor:
     return _ScaleRegFn.apply(scales)
 
 
+AGS_LAYOUT = {"chw": 0, "hwc": 1}      # dnsplat.h DNSPLAT_AGS_LAYOUT_*: [3,H,W] in [-1, 1] | [H,W,3] in [0, 1]
+
+
+class _AgsNormalFn(torch.autograd.Function):
+    """``weight`` x (mean over the selected elements of |surf - gt| + mean over all elements of |pred - gt|) on the normals in [-1, 1]
+    — ``AGSMeshRegularization.get_normal_loss`` (regularization_strategy.py:292-321) — and the selection, in one entry-point call
+    (``dnsplat_ags_normal_loss``: two launches).  ``mode`` 0 selects the elements off the dilated edge map of ``gt``, 1 the pixels whose
+    surface normal is within 0.1 rad of it.  The number selected stays on the device: the value and the gradient divide by it there."""
+
+    @staticmethod
+    def forward(ctx, surf, gt, pred, mode, weight, layout):
+        surf = _f32c(surf, "surf_normal"); gt = _f32c(gt, "gt_normal"); pred = _f32c(pred, "pred_normal")
+        if surf.dim() != 3 or surf.shape[0 if layout == "chw" else 2] != 3 or gt.shape != surf.shape or pred.shape != surf.shape:
+            raise ValueError(f"dnsplat AGS normal loss takes three {'[3,H,W]' if layout == 'chw' else '[H,W,3]'} images, got "
+                             f"{tuple(surf.shape)}, {tuple(gt.shape)}, {tuple(pred.shape)}")
+        H, W = (surf.shape[1], surf.shape[2]) if layout == "chw" else (surf.shape[0], surf.shape[1])
+        dev = surf.device
+        need_s, _, need_p = ctx.needs_input_grad[:3]
+        v_surf = torch.empty_like(surf) if need_s else None
+        v_pred = torch.empty_like(pred) if need_p else None
+        selection = torch.empty((3, H, W) if mode == 0 else (H, W), dtype=torch.bool, device=dev)
+        L = _lib.lib()
+        scratch = torch.empty(L.dnsplat_ags_normal_scratch_bytes(W, H) // 8, dtype=torch.float64, device=dev)
+        sums = torch.empty(2, dtype=torch.float64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.run("dnsplat_ags_normal_loss", L.dnsplat_ags_normal_loss, W, H, _ptr(surf), _ptr(gt), _ptr(pred), AGS_LAYOUT[layout], int(mode),
+                 float(weight), _ptr(v_surf), _ptr(v_pred), _ptr(selection), _ptr(scratch), _ptr(sums), _ptr(count), _stream())
+        ctx.save_for_backward(v_surf, v_pred, count)
+        ctx.mark_non_differentiable(selection)
+        # 0 / 0 = nan for an empty selection, as the reference's mean of nothing; times a weight of 0 it stays nan
+        loss = (sums[0] / count[0]) * weight + (sums[1] / (3.0 * H * W)) * weight
+        return loss.float(), selection
+
+    @staticmethod
+    def backward(ctx, g, _g_selection):
+        v_surf, v_pred, count = ctx.saved_tensors
+        g_surf = g_pred = None
+        if v_surf is not None:
+            # nothing selected: v_surf is all zeros and autograd's gather backward leaves zeros too (not 0 x inf)
+            n = count[0]
+            g_surf = v_surf * torch.where(n > 0, g / n.clamp(min=1), torch.zeros_like(g))
+        if v_pred is not None:
+            g_pred = v_pred * g
+        return g_surf, None, g_pred, None, None, None
+
+
+def ags_normal_loss(surf_normal: Tensor, gt_normal: Tensor, pred_normal: Tensor, step: int, normal_lambda: float = 0.1,
+                    normal_mask_steps: int = 15000, layout: str = "chw", return_selection: bool = False):
+    """``AGSMeshRegularization.get_normal_loss(step, surf_normal, gt_normal, pred_normal)`` (regularization_strategy.py:292-321;
+    ``torch_losses.ags_normal_loss``) without the six conv2d calls of ``find_edges`` and without the two boolean-mask gathers, whose
+    data-dependent size is a host synchronisation each: two launches, nothing read on the host, so the call can be captured.
+    ``layout`` "chw": [3,H,W] tensors in [-1, 1], what the method receives; "hwc": the [H,W,3] images in [0, 1] that ``outputs`` /
+    ``batch`` hold (``2 x - 1`` is applied by the kernel, the gradients are w.r.t. the images).  ``step <= 7000`` takes the same path
+    with weight 0: the value is 0 with zero gradients — or nan where nothing is selected, as in the reference.  Gradients w.r.t.
+    ``surf_normal`` and ``pred_normal``.  ``return_selection``: also the filter map, bool — before ``normal_mask_steps`` [3,H,W], the
+    elements OFF the dilated edge map; from then on [H,W], the confident pixels."""
+    if gt_normal.requires_grad:
+        raise NotImplementedError("dnsplat ags_normal_loss differentiates the surface and the predicted normal only")
+    if layout not in AGS_LAYOUT:
+        raise ValueError(f'layout must be "chw" or "hwc", got {layout!r}')
+    weight = float(normal_lambda) if step > 7000 else 0.0                               # regularization_strategy.py:296
+    loss, selection = _AgsNormalFn.apply(surf_normal, gt_normal, pred_normal, 0 if step < normal_mask_steps else 1, weight, layout)
+    return (loss, selection) if return_selection else loss
+
+
+def ags_mesh_loss_fused(outputs: Dict[str, Tensor], batch: Dict[str, Tensor], scales: Tensor, step: int,
+                        confidence: Optional[Tensor] = None, ssim_lambda: float = 0.2, depth_lambda: float = 0.2,
+                        depth_tolerance: float = 0.1, normal_lambda: float = 0.1, normal_mask_steps: int = 15000) -> Tensor:
+    """main_loss of ``DNSplatterModel.get_loss_dict`` for regularization_strategy == "ags-mesh" (dn_model.py:614-729 with
+    ``AGSMeshRegularization.get_loss``, regularization_strategy.py:233-255; ``torch_losses.ags_mesh_loss``), the counterpart of
+    ``dn_loss_fused``: the rgb term (``dnsplat_dn_loss`` without depth and normal ground truth), ``depth_lambda`` x EdgeAwareLogL1 under
+    the mask ``torch_losses.ags_depth_mask`` (``dnsplat_edge_aware_logl1``), the filtered normal term on the [H,W,3] images as they are
+    (``dnsplat_ags_normal_loss``) and the scale term.  ``confidence``: the confidence MAP, by default ``1 - batch["confidence"] /
+    255`` (:646).  A ``batch["mask"]`` multiplies the rendered depth, the predicted normal and the two ground truths (:648-660; not the
+    surface normal).  Nothing is read on the host: forward and backward can be captured into a HIP graph."""
+    from .torch_losses import ags_depth_mask
+
+    rgb = outputs["rgb"]
+    if not rgb.is_cuda:
+        raise _lib.DnsplatError("ags_mesh_loss_fused runs on the GPU: the tensors are on " + str(rgb.device))
+    depth, normal, surf_normal = outputs["depth"], outputs["normal"], outputs["surface_normal"]
+    gt_depth, gt_normal = batch["mono_depth"], batch["normal"]
+    if confidence is None:
+        confidence = 1 - batch["confidence"] / 255.0
+    if "mask" in batch:
+        mask = batch["mask"]
+        depth, normal, gt_depth, gt_normal = depth * mask, normal * mask, gt_depth * mask, gt_normal * mask
+    gt_img = batch["image"].clamp(min=10 / 255.0)                                        # dn_model.py:633
+    loss = _DnLossFn.apply(rgb, depth.detach(), normal.detach(), batch["image"], None, None, None, ssim_lambda, depth_lambda, depth_tolerance)
+    depth_mask = ags_depth_mask(gt_depth, confidence, step, depth_tolerance).reshape(depth.shape[0], depth.shape[1])
+    loss = loss + _EdgeAwareLogL1Fn.apply(depth, gt_depth, gt_img, depth_mask) * depth_lambda
+    loss = loss + ags_normal_loss(surf_normal, gt_normal, normal, step, normal_lambda, normal_mask_steps, layout="hwc")
+    return loss + _ScaleRegFn.apply(scales)
+
+
 def dn_loss_fused(outputs: Dict[str, Tensor], batch: Dict[str, Tensor], scales: Tensor, ssim_lambda: float = 0.2,
                   depth_lambda: float = 0.2, depth_tolerance: float = 0.1, counts: Optional[Tensor] = None) -> Tensor:
     """Drop-in for ``torch_losses.dn_loss`` (mono depth + mono normal supervision).  A ``batch["mask"]`` multiplies the rendered

@@ -150,8 +150,11 @@ def install_losses(model):
     ``install_ssim(model)``.  A ``DNRegularization`` whose ``depth_loss_type`` is ``PearsonDepth`` builds its local term anew on every
     call (regularization_strategy.py:171), out of reach of a module swap: its ``get_depth_loss`` method is replaced
     (``_hip_pearson_depth_loss``: both Pearson terms in one ``dnsplat_pearson_depth`` call); a holder whose inner module is a
-    ``PearsonDepthLoss`` / ``LocalPearsonDepthLoss`` gets the drop-in of that name.  Everything else of ``get_loss_dict`` stays the
-    reference's PyTorch code.  Returns the list of what was swapped."""
+    ``PearsonDepthLoss`` / ``LocalPearsonDepthLoss`` gets the drop-in of that name.  An
+    ``AGSMeshRegularization``, whose filtered normal term lives in a method as well (regularization_strategy.py:292-321: find_edges'
+    six conv2d calls and two boolean-mask gathers), gets ``get_normal_loss`` replaced by ``_hip_ags_normal_loss`` over
+    ``fused_loss.ags_normal_loss`` (``dnsplat_ags_normal_loss``); its depth term already runs through the swapped EdgeAwareLogL1 module.
+    Everything else of ``get_loss_dict`` stays the reference's PyTorch code.  Returns the list of what was swapped."""
     from . import fused_loss
 
     swapped = []
@@ -191,6 +194,15 @@ def install_losses(model):
 
         strategy.get_depth_loss = _hip_pearson_depth_loss
         swapped.append("regularization_strategy.get_depth_loss")
+    if strategy is not None and type(strategy).__name__ == "AGSMeshRegularization" \
+            and getattr(getattr(strategy, "get_normal_loss", None), "__name__", "") != "_hip_ags_normal_loss":
+        def _hip_ags_normal_loss(step, surf_normal, gt_normal, pred_normal):
+            """regularization_strategy.py:292-321; the weight and the step at which the filter changes are read at call time."""
+            return fused_loss.ags_normal_loss(surf_normal, gt_normal, pred_normal, step, strategy.normal_lambda,
+                                              strategy.normal_mask_steps)
+
+        strategy.get_normal_loss = _hip_ags_normal_loss
+        swapped.append("regularization_strategy.get_normal_loss")
     if hasattr(model, "ssim"):
         install_ssim(model)
         swapped.append("ssim")

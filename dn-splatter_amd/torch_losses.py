@@ -8,6 +8,7 @@ with the renderer; nothing here is a kernel of ours.  It follows
 * ``DNRegularization.get_loss`` / depth / normal / scale dn_splatter/regularization_strategy.py:146-199
 * ``EdgeAwareLogL1``, ``LogL1``, ``L1``, ``TVLoss``      dn_splatter/losses.py:154-224, 279-295
 * ``PearsonDepthLoss``, ``LocalPearsonDepthLoss``        dn_splatter/losses.py:428-485 (depth_loss_type = PearsonDepth)
+* ``AGSMeshRegularization`` depth / normal, ``find_edges``, ``mean_angular_error``   dn_splatter/regularization_strategy.py:11-96, 202-327
 * the inherited RGB term of nerfstudio's ``SplatfactoModel.get_loss_dict``: ``(1 - l) * L1 + l * (1 - SSIM)`` with
   ``l = ssim_lambda = 0.2``; ``self.ssim`` is, in dn-splatter, torchmetrics' ``StructuralSimilarityIndexMeasure(data_range=1.0,
   kernel_size=11)`` (dn_model.py:180; nerfstudio itself holds pytorch_msssim's SSIM): an 11 x 11 Gaussian window, sigma 1.5, averaged
@@ -202,6 +203,99 @@ def pearson_depth_term(pred_depth: Tensor, gt_depth: Tensor, rows: Tensor, cols:
     depth_loss = whole + depth_lambda * local
     depth_loss = depth_loss + depth_lambda * depth_loss
     return depth_loss
+
+
+AGS_LAMBDA_FROM = 7000      # regularization_strategy.py:296 / :261, :274: a literal in the reference
+
+
+def _shifted(t: Tensor, dy: int, dx: int) -> Tensor:
+    """t[..., y + dy, x + dx] with zeros outside the frame (dy, dx in -1, 0, 1) — one tap of a conv2d with padding=1."""
+    p = F.pad(t, (1, 1, 1, 1))
+    H, W = t.shape[-2], t.shape[-1]
+    return p[..., 1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+
+
+def ags_find_edges(gt_normal: Tensor, threshold: float = 0.01) -> Tensor:
+    """``find_edges`` (regularization_strategy.py:40-96) on a [3,H,W] normal map in [-1, 1], bool [3,H,W]: per channel the
+    Laplacian of 1 / (n + 1e-6) with zeros outside the frame — up + down + left + right - 4 r, in this order — above ``threshold``,
+    then one 3 x 3 dilation (zeros outside).  The reference phrases both stencils as one-channel conv2d calls; the taps are written
+    out here, so a component of exactly -1e-6 (r = inf) reaches its four neighbours only and inf - inf = nan compares false."""
+    r = 1.0 / (gt_normal + 1e-6)
+    lap = _shifted(r, -1, 0) + _shifted(r, 1, 0) + _shifted(r, 0, -1) + _shifted(r, 0, 1) - 4 * r
+    e = (lap > threshold).to(torch.uint8)
+    out = torch.zeros_like(e)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            out = out | _shifted(e, dy, dx)
+    return out > 0
+
+
+def ags_normal_confidence(surf_normal: Tensor, gt_normal: Tensor, max_angle: float = 0.1) -> Tensor:
+    """The filter of regularization_strategy.py:299-300, :311 on [3,H,W] normals, bool [H,W]: not (``mean_angular_error`` >
+    0.1 rad), the angle being arccos(clip(sum_c gt_c surf_c, -1, 1)) (:11-26).  A nan dot product is confident."""
+    dot = torch.clip((gt_normal * surf_normal).sum(dim=0), -1.0, 1.0)
+    return ~(torch.arccos(dot) > max_angle)
+
+
+def ags_normal_loss(surf_normal: Tensor, gt_normal: Tensor, pred_normal: Tensor, step: int, normal_lambda: float = 0.1,
+                    normal_mask_steps: int = 15000, selection: Optional[Tensor] = None) -> Tensor:
+    """``AGSMeshRegularization.get_normal_loss`` (regularization_strategy.py:292-321) on [3,H,W] normals in [-1, 1]:
+    lambda = normal_lambda after step 7000, else 0; before ``normal_mask_steps`` the L1 mean of surf - gt over the ELEMENTS off the
+    dilated edge map, from then on over the three channels of the confident pixels; plus the L1 mean of pred - gt over everything;
+    both times lambda.  Two boolean-mask gathers (a host synchronisation each); nothing selected: nan.
+    ``selection``: the mask to use instead of the one computed here — bool [3,H,W] (elements kept) before ``normal_mask_steps``,
+    bool [H,W] (pixels kept) from then on."""
+    lam = normal_lambda if step > AGS_LAMBDA_FROM else 0.0
+    if step < normal_mask_steps:
+        keep = ~ags_find_edges(gt_normal) if selection is None else selection
+        normal_l1 = torch.abs(surf_normal[keep] - gt_normal[keep]).mean() * lam
+    else:
+        keep = ags_normal_confidence(surf_normal, gt_normal) if selection is None else selection
+        normal_l1 = torch.abs(surf_normal[:, keep] - gt_normal[:, keep]).mean() * lam
+    return normal_l1 + torch.abs(pred_normal - gt_normal).mean() * lam
+
+
+def ags_depth_mask(gt_depth: Tensor, confidence: Tensor, step: int, tolerance: float = 0.1) -> Tensor:
+    """The mask ``AGSMeshRegularization.get_depth_loss`` (regularization_strategy.py:257-290) hands to EdgeAwareLogL1: the valid
+    ground-truth depths, from step 7000 on only where the confidence map is positive (there the reference zeroes the other depths
+    first; a ground truth under a false mask is never counted, so the mask alone says it)."""
+    mask = gt_depth > tolerance
+    if step >= AGS_LAMBDA_FROM:
+        mask = mask & (confidence > 0)
+    return mask
+
+
+def ags_regularization_term(outputs: Dict[str, Tensor], batch: Dict[str, Tensor], scales: Tensor, step: int, depth_lambda: float = 0.2,
+                            depth_tolerance: float = 0.1, normal_lambda: float = 0.1, normal_mask_steps: int = 15000) -> Tensor:
+    """What dn-splatter adds in get_loss_dict (dn_model.py:629-727) for regularization_strategy == "ags-mesh" with mono depth and
+    mono normal supervision: ``AGSMeshRegularization.get_loss`` (regularization_strategy.py:233-255) on what the method picks — the
+    image clamped at 10/255 (:633), confidence = 1 - batch["confidence"] / 255 (:646), depth, the predicted normal and the two
+    ground truths times ``batch["mask"]`` (:648-660; the surface normal is not), the three normal images as 2 x - 1 in [3,H,W]
+    (:721-723).  Pinned to the reference's own text: tests/golden/reference_ags.npz."""
+    gt_img = batch["image"].clamp(min=10 / 255.0)
+    depth_out, pred_normal, surf_normal = outputs["depth"], outputs["normal"], outputs["surface_normal"]
+    gt_depth, gt_normal = batch["mono_depth"], batch["normal"]
+    confidence = 1 - batch["confidence"] / 255.0
+    if "mask" in batch:
+        mask = batch["mask"]
+        depth_out, gt_depth, gt_normal, pred_normal = depth_out * mask, gt_depth * mask, gt_normal * mask, pred_normal * mask
+    depth_mask = ags_depth_mask(gt_depth, confidence, step, depth_tolerance)
+    loss = edge_aware_log_l1(depth_out, gt_depth.to(depth_out.dtype), gt_img, depth_mask) * depth_lambda
+
+    def chw(im):
+        return (2 * im - 1).permute(2, 0, 1)
+
+    loss = loss + ags_normal_loss(chw(surf_normal), chw(gt_normal), chw(pred_normal), step, normal_lambda, normal_mask_steps)
+    return loss + torch.min(torch.exp(scales), dim=1, keepdim=True)[0].mean()
+
+
+def ags_mesh_loss(outputs: Dict[str, Tensor], batch: Dict[str, Tensor], scales: Tensor, step: int, ssim_lambda: float = 0.2,
+                  depth_lambda: float = 0.2, depth_tolerance: float = 0.1, normal_lambda: float = 0.1,
+                  normal_mask_steps: int = 15000) -> Tensor:
+    """main_loss of ``DNSplatterModel.get_loss_dict`` for regularization_strategy == "ags-mesh" (dn_model.py:614-729):
+    rgb_loss + regularization_strategy_loss (:727)."""
+    return rgb_term(outputs, batch, ssim_lambda) + ags_regularization_term(outputs, batch, scales, step, depth_lambda, depth_tolerance,
+                                                                           normal_lambda, normal_mask_steps)
 
 
 def _ssim_hip(pred: Tensor, gt: Tensor) -> Tensor:

@@ -54,7 +54,7 @@ extern "C" {
  * Entry points added after 15 are purely additive — new symbols and new structs, no existing struct or call changes — and are found
  * by symbol: the version stays 15 and the binding refuses a library that lacks one (dnsplat_pose_partial_rows,
  * dnsplat_project_bwd_pose / dnsplat_pose_grads: the camera pose gradient; dnsplat_pearson_depth / dnsplat_pearson_scratch_bytes: the
- * Pearson depth losses). */
+ * Pearson depth losses; dnsplat_ags_normal_loss / dnsplat_ags_normal_scratch_bytes: the filtered normal loss of the AGS-Mesh strategy). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -496,6 +496,38 @@ size_t dnsplat_pearson_scratch_bytes(int32_t n_boxes);   /* 0 for n_boxes < 0 */
 int dnsplat_pearson_depth(int32_t width, int32_t height, const float *pred, const float *gt, const uint8_t *mask, int32_t whole,
                           int32_t n_boxes, int32_t box, const int64_t *box_rows, const int64_t *box_cols, float w_whole, float w_box,
                           float *v_pred, void *scratch, float *sums, dnsplat_stream_t stream);
+
+/* Additive in ABI 15 (found by symbol).  The filtered normal loss of the AGS-Mesh regularisation strategy —
+ * AGSMeshRegularization.get_normal_loss (regularization_strategy.py:292-321) with find_edges (:40-96) and mean_angular_error (:11-26) —
+ * in two launches, where the reference runs six one-channel conv2d calls and two boolean-mask gathers (a host synchronisation each).
+ * With n the ground-truth normal in [-1, 1], per channel: r = 1 / (n + 1e-6), lap = up + down + left + right - 4 r with zeros outside
+ * the frame, e = lap > 0.01, E = OR of e over the 3 x 3 neighbourhood (zeros outside); per pixel: C = not (dot(n, surf) < cos 0.1), the
+ * reference's not (arccos(clip(dot, -1, 1)) > 0.1).  Plain IEEE fp32 in the order ((up + down) + left) + right - 4 r: a border pixel
+ * with a negative component is an edge, a component of exactly -1e-6 gives inf, inf - inf is nan and nan > 0.01 is false; a nan dot
+ * product is confident.
+ *   surf, gt, pred   fp32 images of one frame: layout DNSPLAT_AGS_LAYOUT_CHW = [3,H,W] in [-1, 1] (what the method receives),
+ *              DNSPLAT_AGS_LAYOUT_HWC = [H,W,3] in [0, 1] (what outputs / batch hold): 2 x - 1 is applied here, one rounding as torch's.
+ *   mode       0: the mean of |surf - n| runs over the ELEMENTS with ~E; 1: over the three channels of the pixels with C.
+ *   sums       out, device double [2]: sums[0] = sum over the selected elements of |surf - n|, sums[1] = sum over all 3 H W elements of
+ *              |pred - n|.
+ *   count      out, device int64 [1]: the number of selected elements (mode 1: 3 x the confident pixels).  The loss is
+ *              weight * (sums[0] / count + sums[1] / (3 H W)); count == 0 gives 0 / 0 = nan, as the reference's mean of nothing.
+ *   v_surf     out, the shape of surf, or NULL: weight * sgn(surf - n) on the selected elements, 0 elsewhere — d(weight * sums[0]) / d surf;
+ *              the normaliser 1 / count exists on the device only, the caller divides there (as with dnsplat_edge_aware_logl1).
+ *   v_pred     out, the shape of pred, or NULL: weight * sgn(pred - n) / (3 H W), the finished gradient of the second term.
+ *              Both are w.r.t. the tensor as given: in the HWC layout they carry the factor 2 of 2 x - 1.
+ *   selection  out or NULL, bytes (torch.bool): mode 0 [3,H,W] = ~E (planar in either layout), mode 1 [H,W] = C.
+ *   scratch    dnsplat_ags_normal_scratch_bytes(width, height) bytes, 8-byte aligned; contents need not survive.
+ * One partial per workgroup (sums in double, the count an integer), added by a second launch in a fixed order, no atomic: the result
+ * is bit-reproducible.  No allocation, no synchronisation.
+ * Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL surf / gt / pred / scratch / sums / count, width < 1, height < 1, a
+ * layout or a mode other than the two above; DNSPLAT_ERR_UNSUPPORTED for a side above 2^30 or a frame of more than 2^31 - 1 tiles of 64 x 16 pixels. */
+#define DNSPLAT_AGS_LAYOUT_CHW 0
+#define DNSPLAT_AGS_LAYOUT_HWC 1
+size_t dnsplat_ags_normal_scratch_bytes(int32_t width, int32_t height);   /* 0 for width < 1 or height < 1 */
+int dnsplat_ags_normal_loss(int32_t width, int32_t height, const float *surf, const float *gt, const float *pred, int32_t layout,
+                            int32_t mode, float weight, float *v_surf, float *v_pred, uint8_t *selection, void *scratch, double *sums,
+                            int64_t *count, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
