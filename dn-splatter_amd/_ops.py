@@ -1,12 +1,18 @@
-"""Tensor-level wrappers over the C ABI and the two autograd nodes everything else is built from.
+"""Tensor-level wrappers over the C ABI and the autograd nodes everything else is built from.
 
 Graph shape (same cut as gsplat 1.0.0, so the tensors dn-splatter reads back keep their meaning):
 
-    params --_ProjectFn--> means2d, depths, conics, splats --_RasterFn--> render, alphas
-              (stage 1/5)        ^ info["means2d"]: .grad / .absgrad            (stages 2-4)
+    params --_ProjectFn--> means2d, depths, conics, splats --_RasterFn----> render, alphas
+              (stage 1/5)        ^ info["means2d"]: .grad / .absgrad   \\-_RasterDnFn--> rgb, depth, normal, accumulation, surface_normal
+                                                                          (stages 2-4)
 
 ``_ProjectFn`` fuses what gsplat splits into fully_fused_projection + spherical_harmonics and what
-dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rasterize_to_pixels.
+dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rasterize_to_pixels (the drop-in calls);
+``_RasterDnFn`` is the same pass over the 7 fused channels with dn-splatter's per-pixel post-ops inside the kernels (the fused
+get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
+
+One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
+``enqueue``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -331,6 +337,64 @@ def _camera_struct(viewmat, K, normal_frame, cfg: ProjCfg):
     return c
 
 
+class _ShLayout:
+    """How the colours of one projection arrive, resolved once in ``_ProjectFn.forward`` and kept on ``ctx``: ``kind`` "cat" (one
+    tensor ``coeffs`` [N,K,3], gsplat's layout), "split" (``sh0`` [N,3] + ``shN`` [N,K-1,3], the model's own leaves) or "colors"
+    (direct colours, no SH), ``sh_K``, and the row strides band 0 / bands 1.. go to the kernels with.  It holds NO tensor: the
+    inputs are autograd's saved tensors, and a gradient tensor somebody else holds is cloned by autograd instead of adopted as
+    ``.grad`` — ``bands`` turns whichever set it is given (the coefficients, or their gradients) into the kernels' two pointers."""
+    __slots__ = ("kind", "sh_K", "s0", "sN")
+
+    def __init__(self, kind: str, sh_K: int):
+        self.kind, self.sh_K = kind, sh_K
+        self.s0, self.sN = {"cat": (3 * sh_K, 3 * sh_K), "split": (3, 3 * (sh_K - 1)), "colors": (0, 0)}[kind]
+
+    def bands(self, coeffs, sh0, shN, rows=None):
+        """(band 0, bands 1..) of the coefficients — or of their gradients — for the rows ``rows`` = (g0, g1) of the Gaussians."""
+        if rows is not None:
+            coeffs, sh0, shN = (None if t is None else t[rows[0]:rows[1]] for t in (coeffs, sh0, shN))
+        if self.kind == "cat":
+            return coeffs, coeffs.view(-1)[3:]
+        if self.kind == "split":
+            return sh0, (shN if self.sh_K > 1 else None)
+        return None, None
+
+    def scene(self, cfg: ProjCfg, means, quats, scales, opacities, coeffs, sh0, shN, colors, rows=None) -> Scene:
+        p0, pN = self.bands(coeffs, sh0, shN, rows)
+        if rows is not None:
+            means, quats, scales, opacities, colors = (None if t is None else t[rows[0]:rows[1]]
+                                                       for t in (means, quats, scales, opacities, colors))
+        return _scene_struct(means.shape[0], means, quats, scales, opacities, cfg, p0, self.s0, pN, self.sN, self.sh_K, colors)
+
+    def new_grads(self, coeffs, sh0, shN, colors, bucket: bool):
+        """Unwritten [v_coeffs, v_sh0, v_shN, v_colors] (None where the layout has no such input); ``bucket``: the leaves' gradients
+        go where ``_grad_like`` says."""
+        like = _grad_like if bucket else torch.empty_like
+        if self.kind == "cat":
+            return [torch.empty_like(coeffs), None, None, None]
+        if self.kind == "split":
+            return [None, like(sh0), like(shN) if self.sh_K > 1 else None, None]
+        return [None, None, None, None if colors is None else torch.empty_like(colors)]
+
+
+def _proj_grads(lay: _ShLayout, radii, v_splats, cots, geo, sh, rows=None) -> ProjGrads:
+    """``radii`` / ``v_splats`` / ``cots`` = (v_means2d, v_depths, v_conics, v_compensations | None each): one camera's rows;
+    ``geo`` = (v_means, v_quats, v_scales, v_opacities) and ``sh`` = [v_coeffs, v_sh0, v_shN, v_colors]: where the kernel writes.
+    ``rows`` = (g0, g1) restricts every one of them to a slice of the Gaussians (dp.SlicedShExchange)."""
+    v_colors = sh[3]
+    if rows is not None:
+        radii, v_splats, v_colors, *rest = (None if t is None else t[rows[0]:rows[1]] for t in (radii, v_splats, v_colors, *cots, *geo))
+        cots, geo = rest[:4], rest[4:]
+    g = ProjGrads()
+    g.radii, g.v_splats = _ptr(radii), _ptr(v_splats)
+    g.v_means2d, g.v_depths, g.v_conics, g.v_compensations = _ptr(cots[0]), _ptr(cots[1]), _ptr(cots[2]), _ptr(cots[3])
+    g.v_means, g.v_quats, g.v_scales, g.v_opacities = _ptr(geo[0]), _ptr(geo[1]), _ptr(geo[2]), _ptr(geo[3])
+    p0, pN = lay.bands(sh[0], sh[1], sh[2], rows)
+    g.v_sh0, g.v_sh0_stride, g.v_shN, g.v_shN_stride = _ptr(p0), lay.s0, _ptr(pN), lay.sN
+    g.v_colors = _ptr(v_colors)
+    return g
+
+
 class _ProjectFn(torch.autograd.Function):
     """Stage 1 forward / stage 5 backward.  SH coefficients come either as one tensor ``coeffs``
     [N,K,3] (gsplat layout, dn_model.py:466-468 concatenates it) or split ``sh0`` [N,3] +
@@ -344,25 +408,18 @@ class _ProjectFn(torch.autograd.Function):
         viewmat = _f32c(viewmat, "viewmats"); K = _f32c(K, "Ks")
         N = means.shape[0]
         dev = means.device
-        sh_K = 0
-        p_sh0 = p_shN = None
-        s0 = sN = 0
+        lay = _ShLayout("colors", 0)
         if cfg.sh_degree >= 0:
             if coeffs is not None:
                 coeffs = _f32c(coeffs, "colors")
-                sh_K = coeffs.shape[1]
-                p_sh0, s0 = coeffs, 3 * sh_K
-                p_shN, sN = coeffs.view(-1)[3:], 3 * sh_K
+                lay = _ShLayout("cat", coeffs.shape[1])
             else:
                 sh0 = _f32c(sh0, "features_dc")
-                sh_K = 1
-                p_sh0, s0 = sh0, 3
                 if shN is not None and shN.shape[1] > 0:
                     shN = _f32c(shN, "features_rest")
-                    sh_K = 1 + shN.shape[1]
-                    p_shN, sN = shN, 3 * (sh_K - 1)
-            if sh_K < (cfg.sh_degree + 1) ** 2:
-                raise ValueError(f"sh_degree={cfg.sh_degree} needs {(cfg.sh_degree + 1) ** 2} bases, got {sh_K}")
+                lay = _ShLayout("split", 1 + (shN.shape[1] if shN is not None else 0))
+            if lay.sh_K < (cfg.sh_degree + 1) ** 2:
+                raise ValueError(f"sh_degree={cfg.sh_degree} needs {(cfg.sh_degree + 1) ** 2} bases, got {lay.sh_K}")
         elif colors is not None:
             colors = _f32c(colors, "colors")
         if normal_frame is not None:
@@ -389,7 +446,7 @@ class _ProjectFn(torch.autograd.Function):
         splats = torch.empty(C * N, RECORD_FLOATS, dtype=torch.float32, device=dev)
         nworld = torch.empty(C, N, 3, dtype=torch.float32, device=dev) if cfg.want_normals_world else None
 
-        scene = _scene_struct(N, means, quats, scales, opacities, cfg, p_sh0, s0, p_shN, sN, sh_K, colors)
+        scene = lay.scene(cfg, means, quats, scales, opacities, coeffs, sh0, shN, colors)
         # phase 1 here, phase 2 (the SH colours: most of the bytes) on a side stream while this stream goes on to the binning
         # kernels, which leave most of the chip idle; whoever reads the colour channels of the records waits for side["colours_ready"]
         split = bool(cfg.split_colours and side is not None and cfg.sh_degree >= 0)
@@ -424,8 +481,7 @@ class _ProjectFn(torch.autograd.Function):
             side["colours_ready"] = ev
 
         ctx.cfg = cfg
-        ctx.sh_K = sh_K
-        ctx.layout = "cat" if coeffs is not None else ("split" if cfg.sh_degree >= 0 else "colors")
+        ctx.sh = lay
         ctx.save_for_backward(means, quats, scales, opacities, coeffs, sh0, shN, colors, viewmat, K, normal_frame, radii, splats)
         ctx.set_materialize_grads(False)
         empty = torch.empty(0, device=dev)
@@ -439,14 +495,35 @@ class _ProjectFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_means2d, v_depths, v_conics, v_comp, v_splats, _r, _t, _n, _tb, _bx):
-        means, quats, scales, opacities, coeffs, sh0, shN, colors, viewmat, K, normal_frame, radii, splats_fwd = ctx.saved_tensors
-        cfg: ProjCfg = ctx.cfg
-        N = means.shape[0]
-        C = viewmat.shape[0]
+        job = _ProjBwd(ctx, v_means2d, v_depths, v_conics, v_comp, v_splats)
+        step = job.mode()
+        total = step(0)      # running sum over the cameras of a batch (C > 1); a single camera writes its outputs directly
+        for c in range(1, job.C):
+            for acc, t in zip(total, step(c)):
+                if acc is not None:
+                    acc.add_(t)
+        need = ctx.needs_input_grad
+        return tuple(t if (t is not None and need[i]) else None for i, t in enumerate(total)) + (
+            None if job.v_viewmat is None else job.v_viewmat.reshape(ctx.viewmat_shape), None, None, None, None, None)
+
+
+class _ProjBwd:
+    """One call of ``_ProjectFn.backward``: what the cameras of the batch share, and one method per mode of stage 5 — ``plain``,
+    ``zero_state``, ``factors``, ``sliced`` — each of which launches camera ``c`` and returns its gradient list
+    [v_means, v_quats, v_scales, v_opacities, v_coeffs, v_sh0, v_shN, v_colors].  Lives for the call only (it sees the gradient
+    tensors: nothing that outlives the backward may hold them, or autograd clones them instead of adopting them as .grad)."""
+
+    def __init__(self, ctx, v_means2d, v_depths, v_conics, v_comp, v_splats):
+        self.saved = ctx.saved_tensors
+        means, viewmat = self.saved[0], self.saved[8]
+        cfg = self.cfg = ctx.cfg
+        self.lay: _ShLayout = ctx.sh
+        N = self.N = means.shape[0]
+        C = self.C = viewmat.shape[0]
         dev = means.device
         if v_splats is None:
             v_splats = torch.zeros(C * N, RECORD_FLOATS, dtype=torch.float32, device=dev)
-        v_splats = v_splats.contiguous()
+        self.v_splats = v_splats = v_splats.contiguous()
         # The screen-space gradient reaches this node in two parts that are ALWAYS added: columns 0-1 of the gradient records (what
         # the compositing backward accumulated and did not hand to autograd separately, _hand_over_means2d_grad) and whatever
         # autograd delivers for means2d itself (terms the caller hung on info["means2d"], the legacy pass fed with non-detached
@@ -459,156 +536,142 @@ class _ProjectFn(torch.autograd.Function):
         v_dep = v_depths.reshape(C, N).contiguous() if v_depths is not None else None
         v_con = v_conics.reshape(C, N, 3).contiguous() if v_conics is not None else None
         v_cmp = v_comp.reshape(C, N).contiguous() if (v_comp is not None and cfg.antialiased) else None
-        sh_K = ctx.sh_K
-        need = ctx.needs_input_grad
+        self.cots = (v_m2d, v_dep, v_con, v_cmp)
         # the camera pose (gsplat's viewmats.grad; the pose a camera optimiser trains): one [4,4] per camera from the pose twin of the
         # kernel, never summed over cameras and never all-reduced.  Not asked for: exactly the plain launch.
-        v_viewmat = torch.empty(C, 4, 4, dtype=torch.float32, device=dev) if need[8] else None
-        pose_rows = (torch.empty(_lib.lib().dnsplat_pose_partial_rows(N), 16, dtype=torch.float32, device=dev)
-                     if v_viewmat is not None else None)
-        total = None      # running sum over the cameras of a batch (C > 1); a single camera writes its outputs directly
+        self.v_viewmat = torch.empty(C, 4, 4, dtype=torch.float32, device=dev) if ctx.needs_input_grad[8] else None
+        self.pose_rows = (torch.empty(_lib.lib().dnsplat_pose_partial_rows(N), 16, dtype=torch.float32, device=dev)
+                          if self.v_viewmat is not None else None)
+        self.fwd = ProjOut()
+        self.fwd.with_depth_channel = int(cfg.with_depth)
+        self.fwd.with_normal_channels = int(cfg.with_normals)
 
-        for c in range(C):
-            v_means = _grad_like(means) if C == 1 else torch.empty_like(means)
-            v_quats = _grad_like(quats) if C == 1 else torch.empty_like(quats)
-            v_scales = _grad_like(scales) if C == 1 else torch.empty_like(scales)
-            v_opac = _grad_like(opacities) if C == 1 else torch.empty_like(opacities)
-            p_sh0 = p_shN = None
-            s0 = sN = 0
-            g = ProjGrads()
-            v_coeffs = v_sh0 = v_shN = v_colors = None
-            if ctx.layout == "cat":
-                p_sh0, s0 = coeffs, 3 * sh_K
-                p_shN, sN = coeffs.view(-1)[3:], 3 * sh_K
-                v_coeffs = torch.empty_like(coeffs)
-                g.v_sh0, g.v_sh0_stride = _ptr(v_coeffs), 3 * sh_K
-                g.v_shN, g.v_shN_stride = _ptr(v_coeffs.view(-1)[3:]), 3 * sh_K
-            elif ctx.layout == "split":
-                p_sh0, s0 = sh0, 3
-                v_sh0 = _grad_like(sh0) if C == 1 else torch.empty_like(sh0)
-                g.v_sh0, g.v_sh0_stride = _ptr(v_sh0), 3
-                if sh_K > 1:
-                    p_shN, sN = shN, 3 * (sh_K - 1)
-                    v_shN = _grad_like(shN) if C == 1 else torch.empty_like(shN)
-                    g.v_shN, g.v_shN_stride = _ptr(v_shN), 3 * (sh_K - 1)
-            elif colors is not None:
-                v_colors = torch.empty_like(colors)
-                g.v_colors = _ptr(v_colors)
+    def mode(self):
+        """The mode every camera of this call runs in, as the bound method that launches one camera."""
+        # The exchange and the tracked zero rows apply only to the model's own split layout (features_dc / features_rest are the leaf
+        # parameters dp.allreduce_gradients rebuilds into, and the rows of the gradient arena), one camera per rank.  With the
+        # concatenated gsplat layout the coefficient gradient is an intermediate autograd tensor that nobody could fill in
+        # afterwards, so the kernel writes the rows itself.
+        self.ex = ex = SH_EXCHANGE
+        if self.lay.kind == "split" and self.lay.sh_K == 16 and self.C == 1:
+            if ex is not None:
+                return self.sliced if getattr(ex, "slices", 1) > 1 else self.factors
+            if GRAD_ARENA is not None and GRAD_ARENA.sh_state is not None:
+                return self.zero_state
+        return self.plain
 
-            scene = _scene_struct(N, means, quats, scales, opacities, cfg, p_sh0, s0, p_shN, sN, sh_K, colors)
-            cam = _camera_struct(viewmat[c], K[c], None if normal_frame is None else normal_frame[c], cfg)
-            fwd = ProjOut()
-            fwd.with_depth_channel = int(cfg.with_depth)
-            fwd.with_normal_channels = int(cfg.with_normals)
-            vs_c = v_splats[c * N:(c + 1) * N]
-            g.radii, g.v_splats = _ptr(radii[c]), _ptr(vs_c)
-            g.v_means2d = _ptr(v_m2d[c]) if v_m2d is not None else None
-            g.v_depths = _ptr(v_dep[c]) if v_dep is not None else None
-            g.v_conics = _ptr(v_con[c]) if v_con is not None else None
-            g.v_compensations = _ptr(v_cmp[c]) if v_cmp is not None else None
-            g.v_means, g.v_quats, g.v_scales, g.v_opacities = _ptr(v_means), _ptr(v_quats), _ptr(v_scales), _ptr(v_opac)
-            ex = SH_EXCHANGE
-            # Only the model's own split layout (features_dc / features_rest are the leaf parameters dp.allreduce_gradients
-            # rebuilds into), one camera per rank.  With the concatenated gsplat layout the coefficient gradient is an
-            # intermediate autograd tensor that nobody could fill in afterwards, so the kernel writes the rows itself.
-            if ex is not None and ctx.layout == "split" and sh_K == 16 and C == 1 and getattr(ex, "slices", 1) > 1:
-                if v_viewmat is not None:
-                    raise _lib.DnsplatError("a camera pose gradient (viewmats / camera_to_world that requires grad) is not supported "
-                                            "together with dp.SlicedShExchange: its launches cover slices of the Gaussians; use "
-                                            "dp.ShFactorExchange or freeze the pose")
-                # dp.SlicedShExchange: the same entry point on K slices of the Gaussians (every row pointer advanced by g0, N = n_k),
-                # each with its own mini slab.  Under capture (record_only) nothing is launched here: the argument structs stay with
-                # the exchange, graph.GraphedDpStep issues launch k + all-gather k behind each replay; the geometry gradients are
-                # then NOT handed to autograd (None): the launches write the bucket slices, which GraphedDpStep installs as .grad.
-                slabs = ex.begin(N, dev, cfg.sh_degree, sh_K, means=means)
-                # what the recorded launches read must stay allocated (graph-pool tensors of the captured backward).  NOT the gradient
-                # tensors: they are slices of the bucket, which outlives the step — and autograd adopts a returned gradient as .grad
-                # only while nobody else holds it (a second reference here made it clone v_sh0 / v_shN out of the bucket)
-                launches, keep = [], [means, quats, scales, opacities, sh0, shN, viewmat, K, normal_frame, radii, vs_c, v_m2d, v_dep, v_con,
-                                      v_cmp, slabs]
-                if ex.record_only and (GRAD_ARENA is None or not all(GRAD_ARENA.holds(t) for t in (v_means, v_quats, v_scales, v_opac, v_sh0, v_shN))):
-                    raise _lib.DnsplatError("the sliced exchange in recorded mode needs the gradients in a dp.GradArena (set_grad_arena) "
-                                            "and .grad = None when the captured backward starts")
-                for k, (g0, g1) in enumerate(ex.bounds):
-                    sc_k = _scene_struct(g1 - g0, means[g0:g1], quats[g0:g1], scales[g0:g1], opacities[g0:g1], cfg, sh0[g0:g1], 3,
-                                         shN[g0:g1], 3 * (sh_K - 1), sh_K, None)
-                    g_k = ProjGrads()
-                    g_k.radii, g_k.v_splats = _ptr(radii[c][g0:g1]), _ptr(vs_c[g0:g1])
-                    g_k.v_means2d = _ptr(v_m2d[c][g0:g1]) if v_m2d is not None else None
-                    g_k.v_depths = _ptr(v_dep[c][g0:g1]) if v_dep is not None else None
-                    g_k.v_conics = _ptr(v_con[c][g0:g1]) if v_con is not None else None
-                    g_k.v_compensations = _ptr(v_cmp[c][g0:g1]) if v_cmp is not None else None
-                    g_k.v_means, g_k.v_quats = _ptr(v_means[g0:g1]), _ptr(v_quats[g0:g1])
-                    g_k.v_scales, g_k.v_opacities = _ptr(v_scales[g0:g1]), _ptr(v_opac[g0:g1])
-                    g_k.v_sh0, g_k.v_sh0_stride = _ptr(v_sh0[g0:g1]), 3
-                    g_k.v_shN, g_k.v_shN_stride = _ptr(v_shN[g0:g1]), 3 * (sh_K - 1)
-                    g_k.sh_factors, g_k.sh_grads_skip = _ptr(slabs[k]), 1
-                    launches.append((ctypes.byref(sc_k), ctypes.byref(cam), ctypes.byref(fwd), ctypes.byref(g_k)))
-                    keep += [sc_k, g_k]
-                keep += [cam, fwd, scene]
-                if ex.record_only:
-                    ex.record(launches, keep)
-                    v_means = v_quats = v_scales = v_opac = None
-                else:
-                    # eager: slab k's all-gather is queued right behind launch k, so it travels while slices k+1.. compute
-                    works = []
-                    for k, args in enumerate(launches):
-                        _lib.run("dnsplat_project_bwd", _lib.lib().dnsplat_project_bwd, *args, _stream())
-                        works.append(ex.gather_slice(k))
-                    ex.works = works
-                outs = [v_means, v_quats, v_scales, v_opac, v_coeffs, v_sh0, v_shN, v_colors]
-                total = outs
-                continue
-            if ex is not None and ctx.layout == "split" and sh_K == 16 and C == 1:
-                # The coefficient-gradient tensors are handed to autograd unwritten; dp.allreduce_gradients fills them.  The
-                # factors come from their own small kernel so that their all-gather is already under way while the geometry
-                # gradients are computed below.
-                fac = ex.begin(N, dev, cfg.sh_degree, sh_K, means=means)
-                own = ex.use_own_rows()
-                if ex.packed:
-                    # slabs of visible rows only: header, masks and block offsets from the forward's radii (two small launches),
-                    # the rows from dnsplat_project_bwd itself
-                    if ex.scratch is None or ex.scratch.numel() < (N + 63) // 64 or ex.scratch.device != dev:
-                        ex.scratch = torch.empty((N + 63) // 64, dtype=torch.int32, device=dev)
-                    _lib.run("dnsplat_visible_index", _lib.lib().dnsplat_visible_index, N, ex.packed_capacity(N), _ptr(radii[c]),
-                             _ptr(viewmat[c]), _ptr(fac), _ptr(ex.scratch), _stream())
-                    g.sh_packed = _ptr(fac)
-                elif ex.deferred or own:
-                    # a captured step (graph.GraphedDpStep): the exchange only starts behind the replay, so nothing is gained by
-                    # having the slab early — dnsplat_project_bwd writes it from the values it holds anyway (one launch less)
-                    g.sh_factors = _ptr(fac)
-                else:
-                    _lib.run("dnsplat_sh_factors", _lib.lib().dnsplat_sh_factors, N, _ptr(radii[c]), _ptr(viewmat[c]),
-                             _ptr(splats_fwd), _ptr(vs_c), _ptr(fac), _stream())
-                    ex.launch()
-                if own:
-                    # this camera's rows as on a single GPU, pre-scaled by 1 / world; the exchange adds the other cameras' shares
-                    from . import dp as _dp
-                    g.sh_grad_scale = ex.scale_override if ex.scale_override is not None else _dp.reduction_scale(_dp.world_size(ex.group))
-                else:
-                    g.sh_grads_skip = 1
-            elif (ex is None and GRAD_ARENA is not None and GRAD_ARENA.sh_state is not None and ctx.layout == "split" and sh_K == 16
-                  and C == 1 and GRAD_ARENA.holds(v_sh0) and GRAD_ARENA.holds(v_shN)):
-                # the rows land in the flat bucket, whose zero rows are tracked: a Gaussian that is culled again is not re-zeroed
-                g.sh_zero_state = _ptr(GRAD_ARENA.sh_state)
-                g.zero_state_geometry = int(all(GRAD_ARENA.holds(t) for t in (v_means, v_quats, v_scales, v_opac)))
-            if v_viewmat is not None:
-                pg = PoseGrads()
-                pg.partials, pg.v_viewmat = _ptr(pose_rows), _ptr(v_viewmat[c])
-                _lib.run("dnsplat_project_bwd_pose", _lib.lib().dnsplat_project_bwd_pose, ctypes.byref(scene), ctypes.byref(cam),
-                         ctypes.byref(fwd), ctypes.byref(g), ctypes.byref(pg), _stream())
-            else:
-                _lib.run("dnsplat_project_bwd", _lib.lib().dnsplat_project_bwd, ctypes.byref(scene), ctypes.byref(cam), ctypes.byref(fwd),
-                         ctypes.byref(g), _stream())
-            outs = [v_means, v_quats, v_scales, v_opac, v_coeffs, v_sh0, v_shN, v_colors]
-            if total is None:
-                total = outs
-            else:
-                for acc, t in zip(total, outs):
-                    if acc is not None:
-                        acc.add_(t)
-        return tuple(t if (t is not None and need[i]) else None for i, t in enumerate(total)) + (
-            None if v_viewmat is None else v_viewmat.reshape(ctx.viewmat_shape), None, None, None, None, None)
+    def camera(self, c):
+        # -> Camera, this camera's rows of radii / v_splats / the cotangents, the unwritten gradient tensors geo + sh
+        means, quats, scales, opacities, coeffs, sh0, shN, colors, viewmat, K, normal_frame, radii = self.saved[:12]
+        N, bucket = self.N, self.C == 1
+        like = _grad_like if bucket else torch.empty_like
+        geo = [like(means), like(quats), like(scales), like(opacities)]        # _grad_like: once per tensor, in this order
+        sh = self.lay.new_grads(coeffs, sh0, shN, colors, bucket)
+        cam = _camera_struct(viewmat[c], K[c], None if normal_frame is None else normal_frame[c], self.cfg)
+        cots = tuple(None if t is None else t[c] for t in self.cots)
+        return cam, radii[c], self.v_splats[c * N:(c + 1) * N], cots, geo, sh
+
+    def launch(self, c, cam, g):
+        scene = self.lay.scene(self.cfg, *self.saved[:8])
+        if self.v_viewmat is not None:
+            pg = PoseGrads()
+            pg.partials, pg.v_viewmat = _ptr(self.pose_rows), _ptr(self.v_viewmat[c])
+            _lib.run("dnsplat_project_bwd_pose", _lib.lib().dnsplat_project_bwd_pose, ctypes.byref(scene), ctypes.byref(cam),
+                     ctypes.byref(self.fwd), ctypes.byref(g), ctypes.byref(pg), _stream())
+        else:
+            _lib.run("dnsplat_project_bwd", _lib.lib().dnsplat_project_bwd, ctypes.byref(scene), ctypes.byref(cam), ctypes.byref(self.fwd),
+                     ctypes.byref(g), _stream())
+
+    def plain(self, c):
+        cam, radii, vs, cots, geo, sh = self.camera(c)
+        self.launch(c, cam, _proj_grads(self.lay, radii, vs, cots, geo, sh))
+        return geo + sh
+
+    def zero_state(self, c):
+        cam, radii, vs, cots, geo, sh = self.camera(c)
+        g = _proj_grads(self.lay, radii, vs, cots, geo, sh)
+        arena = GRAD_ARENA
+        if arena.holds(sh[1]) and arena.holds(sh[2]):
+            # the rows land in the flat bucket, whose zero rows are tracked: a Gaussian that is culled again is not re-zeroed
+            g.sh_zero_state = _ptr(arena.sh_state)
+            g.zero_state_geometry = int(all(arena.holds(t) for t in geo))
+        self.launch(c, cam, g)
+        return geo + sh
+
+    def factors(self, c):
+        # dp.ShFactorExchange: the coefficient-gradient tensors are handed to autograd unwritten; dp.allreduce_gradients fills them.
+        # The factors come from their own small kernel so that their all-gather is already under way while the geometry gradients
+        # are computed.
+        ex = self.ex
+        cam, radii, vs, cots, geo, sh = self.camera(c)
+        g = _proj_grads(self.lay, radii, vs, cots, geo, sh)
+        means, viewmat, splats_fwd = self.saved[0], self.saved[8], self.saved[12]
+        N, dev = self.N, means.device
+        fac = ex.begin(N, dev, self.cfg.sh_degree, self.lay.sh_K, means=means)
+        own = ex.use_own_rows()
+        if ex.packed:
+            # slabs of visible rows only: header, masks and block offsets from the forward's radii (two small launches),
+            # the rows from dnsplat_project_bwd itself
+            if ex.scratch is None or ex.scratch.numel() < (N + 63) // 64 or ex.scratch.device != dev:
+                ex.scratch = torch.empty((N + 63) // 64, dtype=torch.int32, device=dev)
+            _lib.run("dnsplat_visible_index", _lib.lib().dnsplat_visible_index, N, ex.packed_capacity(N), _ptr(radii),
+                     _ptr(viewmat[c]), _ptr(fac), _ptr(ex.scratch), _stream())
+            g.sh_packed = _ptr(fac)
+        elif ex.deferred or own:
+            # a captured step (graph.GraphedDpStep): the exchange only starts behind the replay, so nothing is gained by
+            # having the slab early — dnsplat_project_bwd writes it from the values it holds anyway (one launch less)
+            g.sh_factors = _ptr(fac)
+        else:
+            _lib.run("dnsplat_sh_factors", _lib.lib().dnsplat_sh_factors, N, _ptr(radii), _ptr(viewmat[c]),
+                     _ptr(splats_fwd), _ptr(vs), _ptr(fac), _stream())
+            ex.launch()
+        if own:
+            # this camera's rows as on a single GPU, pre-scaled by 1 / world; the exchange adds the other cameras' shares
+            from . import dp as _dp
+            g.sh_grad_scale = ex.scale_override if ex.scale_override is not None else _dp.reduction_scale(_dp.world_size(ex.group))
+        else:
+            g.sh_grads_skip = 1
+        self.launch(c, cam, g)
+        return geo + sh
+
+    def sliced(self, c):
+        # dp.SlicedShExchange: the same entry point on K slices of the Gaussians (every row pointer advanced by g0, N = n_k),
+        # each with its own mini slab.  Under capture (record_only) nothing is launched here: the argument structs stay with
+        # the exchange, graph.GraphedDpStep issues launch k + all-gather k behind each replay; the geometry gradients are
+        # then NOT handed to autograd (None): the launches write the bucket slices, which GraphedDpStep installs as .grad.
+        ex = self.ex
+        if self.v_viewmat is not None:
+            raise _lib.DnsplatError("a camera pose gradient (viewmats / camera_to_world that requires grad) is not supported "
+                                    "together with dp.SlicedShExchange: its launches cover slices of the Gaussians; use "
+                                    "dp.ShFactorExchange or freeze the pose")
+        cam, radii, vs, cots, geo, sh = self.camera(c)
+        means = self.saved[0]
+        slabs = ex.begin(self.N, means.device, self.cfg.sh_degree, self.lay.sh_K, means=means)
+        # what the recorded launches read must stay allocated (graph-pool tensors of the captured backward).  NOT the gradient
+        # tensors: they are slices of the bucket, which outlives the step — and autograd adopts a returned gradient as .grad
+        # only while nobody else holds it (a second reference here made it clone v_sh0 / v_shN out of the bucket)
+        keep = [*self.saved[:4], *self.saved[5:7], *self.saved[8:12], vs, *self.cots, slabs]
+        if ex.record_only and (GRAD_ARENA is None or not all(GRAD_ARENA.holds(t) for t in (*geo, sh[1], sh[2]))):
+            raise _lib.DnsplatError("the sliced exchange in recorded mode needs the gradients in a dp.GradArena (set_grad_arena) "
+                                    "and .grad = None when the captured backward starts")
+        launches = []
+        for k, rows in enumerate(ex.bounds):
+            sc_k = self.lay.scene(self.cfg, *self.saved[:8], rows=rows)
+            g_k = _proj_grads(self.lay, radii, vs, cots, geo, sh, rows=rows)
+            g_k.sh_factors, g_k.sh_grads_skip = _ptr(slabs[k]), 1
+            launches.append((ctypes.byref(sc_k), ctypes.byref(cam), ctypes.byref(self.fwd), ctypes.byref(g_k)))
+            keep += [sc_k, g_k]
+        keep += [cam, self.fwd]
+        if ex.record_only:
+            ex.record(launches, keep)
+            return [None] * 4 + sh
+        # eager: slab k's all-gather is queued right behind launch k, so it travels while slices k+1.. compute
+        works = []
+        for k, args in enumerate(launches):
+            _lib.run("dnsplat_project_bwd", _lib.lib().dnsplat_project_bwd, *args, _stream())
+            works.append(ex.gather_slice(k))
+        ex.works = works
+        return geo + sh
 
 
 def project(means, quats, scales, opacities, *, coeffs=None, sh0=None, shN=None, colors=None, viewmat, K,
@@ -684,8 +747,13 @@ def bin_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tiles: Tensor, wid
     n_dev = torch.empty(1, dtype=torch.int64, device=dev)
     n_host = BUFFERS.pinned_i64(dev)
     key = (dev, N, width, height)
+    skey = _Buffers._key(dev) + key      # the "static" policy's records are per (device, stream) and frame size
 
-    def make_args(capacity, flatten_ids, tile_offsets):
+    prepared_ws = None      # the workspace dnsplat_bin_prepare last ran on in this call
+
+    def prepare(capacity, flatten_ids, host_slot):
+        """The arguments for lists of ``capacity`` entries; runs the depth sort unless this call has done so on the same workspace."""
+        nonlocal prepared_ws
         nbytes = lib.dnsplat_bin_workspace_bytes(N, capacity, T)
         ws = BUFFERS.workspace(dev, nbytes)
         a = BinArgs()
@@ -693,93 +761,69 @@ def bin_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tiles: Tensor, wid
         a.means2d, a.radii, a.depths, a.tiles_per_gauss = _ptr(means2d), _ptr(radii), _ptr(depths), _ptr(tiles)
         a.isect_capacity = capacity
         a.flatten_ids, a.tile_offsets = _ptr(flatten_ids), _ptr(tile_offsets)
-        a.n_isects, a.n_isects_host = _ptr(n_dev), ctypes.c_void_p(n_host.data_ptr())
+        a.n_isects, a.n_isects_host = _ptr(n_dev), _ptr(host_slot)
         a.workspace, a.workspace_bytes = _ptr(ws), ws.numel()
         # ``tiles`` were counted over the tight boxes (ProjCfg.tight_tiles): the emit kernel rebuilds them from the records
         a.splats, a.tight_tiles = _ptr(tight_splats), int(tight_splats is not None)
         # the fused path keeps its lists to itself: [start, end) per tile instead of gsplat's offsets (no fill launch)
         a.tile_ends, a.skip_offsets_fill = _ptr(tile_ends), int(tile_ends is not None)
         a.tile_boxes = _ptr(tile_boxes)          # the boxes ``tiles`` were counted over, from the same projection
-        a.n_isects_max = _ptr(BUFFERS.n_max.get(_Buffers._key(dev) + key))
-        return a, ws
+        a.n_isects_max = _ptr(BUFFERS.n_max.get(skey))
+        # the N-sized front of the workspace has the same layout for every capacity, so a depth sort done earlier in this call
+        # stays valid for a later emit as long as the buffer was not re-allocated
+        if prepared_ws is None or prepared_ws.data_ptr() != ws.data_ptr():
+            _lib.run("dnsplat_bin_prepare", lib.dnsplat_bin_prepare, ctypes.byref(a), _stream())
+            prepared_ws = ws
+        return a
+
+    def enqueue(capacity, n_isects, host_slot=n_host, event=None, pending=None) -> Binning:
+        """Depth sort (unless this call has done it), ``event`` recorded behind it (the count is on its way to ``host_slot`` then),
+        emit + tile sort into fresh lists of ``capacity`` entries, ``after_emit``."""
+        flatten_ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+        args = prepare(capacity, flatten_ids, host_slot)
+        if event is not None:
+            event.record()
+        _lib.run("dnsplat_bin_emit_sort", lib.dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
+        if pending is not None:
+            pending.ring["pending"].append(pending)
+        b = Binning(flatten_ids, tile_offsets, n_isects, tw, th, n_cameras, pending=pending, tile_ends=tile_ends, n_dev=n_dev)
+        if after_emit is not None:
+            after_emit(b)
+        return b
 
     tile_offsets = torch.empty(T + 1, dtype=torch.int32, device=dev)
     tile_ends = torch.empty(T, dtype=torch.int32, device=dev) if want_ends else None
     mode = BIN_POLICY["mode"]
-    if mode == "deferred" and not defer_ok:
+    if mode in ("deferred", "static") and not defer_ok:
         mode = "capacity"      # callers that hand n_isects / flatten_ids[:n] straight back (the drop-in calls) gain nothing from deferring
     hint = BUFFERS.capacity_hint.get(key, 0)
-    if mode == "static" and not defer_ok:
-        mode = "capacity"
     if mode == "static" and hint:
         # nothing on the host depends on the count (a frame captured into a HIP graph): the capacity is the hint, and the
         # device keeps a running maximum of n_isects that static_overflow() compares with it whenever the caller likes
-        if _Buffers._key(dev) + key not in BUFFERS.n_max:
-            BUFFERS.n_max[_Buffers._key(dev) + key] = torch.zeros(1, dtype=torch.int64, device=dev)
-        capacity = hint
-        sk = _Buffers._key(dev) + key
-        BUFFERS.static_cap[sk] = min(BUFFERS.static_cap.get(sk, capacity), capacity)      # the smallest buffers any such frame got
-        flatten_ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-        args, _ = make_args(capacity, flatten_ids, tile_offsets)
-        args.n_isects_host = None
-        _lib.run("dnsplat_bin_prepare", _lib.lib().dnsplat_bin_prepare, ctypes.byref(args), _stream())
-        _lib.run("dnsplat_bin_emit_sort", _lib.lib().dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
-        b = Binning(flatten_ids, tile_offsets, None, tw, th, n_cameras, tile_ends=tile_ends, n_dev=n_dev)
-        if after_emit is not None:
-            after_emit(b)
-        return b
+        if skey not in BUFFERS.n_max:
+            BUFFERS.n_max[skey] = torch.zeros(1, dtype=torch.int64, device=dev)
+        BUFFERS.static_cap[skey] = min(BUFFERS.static_cap.get(skey, hint), hint)      # the smallest buffers any such frame got
+        return enqueue(hint, None, host_slot=None)
     if mode == "deferred" and hint:
         verify_pending_counts(dev)                     # earlier frames whose count has arrived meanwhile (no wait)
         ring, slot, ev = BUFFERS.ring_slot(dev)
-        n_host = slot
-        capacity = hint
-        flatten_ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-        args, _ = make_args(capacity, flatten_ids, tile_offsets)
-        _lib.run("dnsplat_bin_prepare", _lib.lib().dnsplat_bin_prepare, ctypes.byref(args), _stream())
-        ev.record()
-        _lib.run("dnsplat_bin_emit_sort", _lib.lib().dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
-        pend = _PendingCount(ring, slot, ev, capacity, key)
-        ring["pending"].append(pend)
-        b = Binning(flatten_ids, tile_offsets, None, tw, th, n_cameras, pending=pend, tile_ends=tile_ends, n_dev=n_dev)
-        if after_emit is not None:
-            after_emit(b)
-        return b
+        return enqueue(hint, None, host_slot=slot, event=ev, pending=_PendingCount(ring, slot, ev, hint, key))
     if mode == "capacity" and hint:
-        capacity = hint
-        flatten_ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-        args, ws0 = make_args(capacity, flatten_ids, tile_offsets)
-        _lib.run("dnsplat_bin_prepare", _lib.lib().dnsplat_bin_prepare, ctypes.byref(args), _stream())
         ev = torch.cuda.Event()
-        ev.record()
-        _lib.run("dnsplat_bin_emit_sort", _lib.lib().dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
-        b = Binning(flatten_ids, tile_offsets, -1, tw, th, n_cameras, tile_ends=tile_ends, n_dev=n_dev)
-        if after_emit is not None:
-            after_emit(b)
+        b = enqueue(hint, -1, event=ev)
         ev.synchronize()  # waits for the (early) depth sort only; compositing keeps running
         n = int(n_host.item())
-        if n <= capacity:
+        if n <= hint:
             b.n_isects = n
             BUFFERS.capacity_hint[key] = max(hint, int(n * 1.25) + 4096)
             return b
         # guess too small: fall through and redo with the exact size
     else:
-        # the N-sized front of the workspace has the same layout for every capacity, so the depth sort
-        # done here stays valid for the emit below as long as the buffer is not re-allocated
-        args, ws0 = make_args(hint, None, tile_offsets)
-        _lib.run("dnsplat_bin_prepare", _lib.lib().dnsplat_bin_prepare, ctypes.byref(args), _stream())
+        prepare(hint, None, n_host)      # the depth sort alone: the host reads the count before anything is emitted
         torch.cuda.current_stream().synchronize()
         n = int(n_host.item())
-    capacity = n
     BUFFERS.capacity_hint[key] = max(hint, int(n * 1.25) + 4096)
-    flatten_ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    args, ws1 = make_args(capacity, flatten_ids, tile_offsets)
-    if ws1.data_ptr() != ws0.data_ptr():
-        _lib.run("dnsplat_bin_prepare", _lib.lib().dnsplat_bin_prepare, ctypes.byref(args), _stream())
-    _lib.run("dnsplat_bin_emit_sort", _lib.lib().dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
-    b = Binning(flatten_ids, tile_offsets, n, tw, th, n_cameras, tile_ends=tile_ends, n_dev=n_dev)
-    if after_emit is not None:
-        after_emit(b)
-    return b
+    return enqueue(n, n)
 
 
 class LazyInfo(dict):
@@ -918,6 +962,52 @@ def _hand_over_means2d_grad(means2d: Tensor, v_splats: Tensor):
     return None
 
 
+def _raster_args(C, width, height, tile_size, D, ed_channel, background, splats, flatten_ids, tile_offsets, tile_ends, render, alphas,
+                 last_ids) -> RasterArgs:
+    """What every compositing launch takes, forward or backward, drop-in or fused; the caller adds what only it has."""
+    a = RasterArgs()
+    a.n_cameras = C
+    a.width, a.height, a.tile_size, a.D = width, height, tile_size, D
+    a.splats, a.flatten_ids, a.tile_offsets, a.tile_ends = _ptr(splats), _ptr(flatten_ids), _ptr(tile_offsets), _ptr(tile_ends)
+    a.background = _ptr(background)
+    a.ed_channel = ed_channel
+    a.render, a.alphas, a.last_ids = _ptr(render), _ptr(alphas), _ptr(last_ids)
+    return a
+
+
+def _bin_for(holder, composite, means2d, splats, depths, radii, tiles, width, height, tile_size, C, fused: bool) -> Binning:
+    # stage 2 for a compositing node: ``composite(binning)`` is queued right behind the sort (bin_tiles' ``after_emit``).  The fused
+    # path keeps its lists to itself: [start, end) per tile, and a count the host need not wait for
+    tight = bool(holder is not None and holder.get("tight"))      # ``tiles`` were counted over the tight boxes
+    b = bin_tiles(means2d.detach().reshape(-1, 2), radii.reshape(-1), depths.detach().reshape(-1), tiles.reshape(-1), width,
+                  height, tile_size, after_emit=composite, n_cameras=C, tight_splats=splats.detach() if tight else None,
+                  defer_ok=fused, want_ends=fused, tile_boxes=holder.get("tile_boxes") if holder is not None else None)
+    if holder is not None:
+        holder["binning"] = b
+    return b
+
+
+def _tile_boxes_into(holder, tight, tile_boxes):
+    """``tiles`` / ``tight`` / ``tile_boxes``: ``tiles_bin``, ``tight_tiles`` and ``tile_boxes`` of the project() result, always taken
+    together (the binning walks the boxes the counts were taken over) — they travel to the node in ``holder``."""
+    if tight or tile_boxes is not None:
+        holder = {} if holder is None else holder
+        holder["tight"] = bool(tight)
+        holder["tile_boxes"] = tile_boxes          # (first tile, width) per entry, of the same projection as ``tiles``
+    return holder
+
+
+def _composite_bwd(a: RasterArgs, b: Binning, means2d: Tensor, v_splats: Tensor, absgrad: bool, det: bool = True):
+    """Launches the compositing backward over ``a``; returns the gradient to hand to autograd for ``means2d``."""
+    part = _det_begin(a, b, v_splats.device) if det else None
+    _lib.run("dnsplat_raster_bwd", _lib.lib().dnsplat_raster_bwd, ctypes.byref(a), _stream())
+    _det_finish(part, b, v_splats)
+    if absgrad:
+        # gsplat contract (dn_model.py:512, consumed by nerfstudio after_train via self.xys.absgrad)
+        means2d.absgrad = v_splats[:, 14:16].reshape(means2d.shape)
+    return _hand_over_means2d_grad(means2d, v_splats)
+
+
 class _RasterFn(torch.autograd.Function):
     """Bins, then composites D channels.  ``means2d`` is an input only so that autograd routes the
     xy-gradient through the tensor dn-splatter calls retain_grad() on (dn_model.py:517-519); the
@@ -934,21 +1024,11 @@ class _RasterFn(torch.autograd.Function):
         bg = _f32c(background, "background") if background is not None else None
 
         def composite(b: Binning):
-            a = RasterArgs()
-            a.n_cameras = C
-            a.width, a.height, a.tile_size, a.D = width, height, tile_size, D
-            a.splats, a.flatten_ids, a.tile_offsets = _ptr(splats), _ptr(b.flatten_ids), _ptr(b.tile_offsets)
-            a.background = _ptr(bg)
-            a.ed_channel = ed_channel
-            a.render, a.alphas, a.last_ids = _ptr(render), _ptr(alphas), _ptr(last_ids)
+            a = _raster_args(C, width, height, tile_size, D, ed_channel, bg, splats, b.flatten_ids, b.tile_offsets, None, render, alphas,
+                             last_ids)
             _lib.run("dnsplat_raster_fwd", _lib.lib().dnsplat_raster_fwd, ctypes.byref(a), _stream())
 
-        tight = bool(holder is not None and holder.get("tight"))      # ``tiles`` were counted over the tight boxes
-        b = bin_tiles(means2d.detach().reshape(-1, 2), radii.reshape(-1), depths.detach().reshape(-1), tiles.reshape(-1), width,
-                      height, tile_size, after_emit=composite, n_cameras=C, tight_splats=splats.detach() if tight else None,
-                      tile_boxes=holder.get("tile_boxes") if holder is not None else None)
-        if holder is not None:
-            holder["binning"] = b
+        b = _bin_for(holder, composite, means2d, splats, depths, radii, tiles, width, height, tile_size, C, fused=False)
         ctx.save_for_backward(means2d, splats, b.flatten_ids, b.tile_offsets, render, alphas, last_ids)
         ctx.bg = bg
         ctx.binning = b
@@ -969,34 +1049,15 @@ class _RasterFn(torch.autograd.Function):
             v_render = torch.zeros_like(render)
         v_render = v_render.contiguous()
         v_alphas = v_alphas.contiguous() if v_alphas is not None else None
-        a = RasterArgs()
-        a.n_cameras = C
-        a.width, a.height, a.tile_size, a.D = width, height, tile_size, D
-        a.splats, a.flatten_ids, a.tile_offsets = _ptr(splats), _ptr(flatten_ids), _ptr(tile_offsets)
-        a.background = _ptr(ctx.bg)
-        a.ed_channel = ed_channel
-        a.render, a.alphas, a.last_ids = _ptr(render), _ptr(alphas), _ptr(last_ids)
-        a.v_render, a.v_alphas = _ptr(v_render), _ptr(v_alphas)
-        a.xy_split = xy_split
-        a.v_splats = _ptr(v_splats)
-        det = _det_begin(a, ctx.binning, dev)
-        _lib.run("dnsplat_raster_bwd", _lib.lib().dnsplat_raster_bwd, ctypes.byref(a), _stream())
-        _det_finish(det, ctx.binning, v_splats)
-        if absgrad:
-            # gsplat contract (dn_model.py:512, consumed by nerfstudio after_train via self.xys.absgrad)
-            means2d.absgrad = v_splats[:, 14:16].reshape(means2d.shape)
-        return (_hand_over_means2d_grad(means2d, v_splats), v_splats) + (None,) * 12
+        a = _raster_args(C, width, height, tile_size, D, ed_channel, ctx.bg, splats, flatten_ids, tile_offsets, None, render, alphas, last_ids)
+        a.v_render, a.v_alphas, a.xy_split, a.v_splats = _ptr(v_render), _ptr(v_alphas), xy_split, _ptr(v_splats)
+        return (_composite_bwd(a, ctx.binning, means2d, v_splats, absgrad), v_splats) + (None,) * 12
 
 
 def rasterize(means2d, splats, depths, radii, tiles, *, background=None, width, height, tile_size=16, D,
               ed_channel=-1, xy_split=None, absgrad=False, holder=None, tight=False, tile_boxes=None):
-    """-> render [C,H,W,D], alphas [C,H,W] for the C cameras of ``means2d`` [C,N,2] / ``splats`` [C*N,16].
-    ``tiles`` / ``tight``: ``tiles_bin`` and ``tight_tiles`` of the project() result, always taken together (the binning walks the
-    boxes the counts were taken over)."""
-    if tight or tile_boxes is not None:
-        holder = {} if holder is None else holder
-        holder["tight"] = bool(tight)
-        holder["tile_boxes"] = tile_boxes          # (first tile, width) per entry, of the same projection as ``tiles``
+    """-> render [C,H,W,D], alphas [C,H,W] for the C cameras of ``means2d`` [C,N,2] / ``splats`` [C*N,16]."""
+    holder = _tile_boxes_into(holder, tight, tile_boxes)
     if tile_size != 16:
         raise NotImplementedError("libdnsplat composites 16x16 tiles (dn_model.py:470-472 uses BLOCK_WIDTH = 16)")
     if xy_split is None:
@@ -1047,7 +1108,6 @@ class _RasterDnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, splats, depths, radii, tiles, bg_rgb, width, height, intr, absgrad, holder):
         dev = splats.device
-        tight = bool(holder is not None and holder.get("tight"))
         ctx.saturation_flag = holder.get("saturation_flag") if holder is not None else None
         C = means2d.shape[0]                     # cameras of the batch; intr = [(fx, fy, cx, cy)] * C
         f32 = dict(dtype=torch.float32, device=dev)
@@ -1087,35 +1147,23 @@ class _RasterDnFn(torch.autograd.Function):
             ready = holder.get("colours_ready") if holder is not None else None
             if ready is not None:          # the projection's colour phase runs on a side stream (ProjCfg.split_colours)
                 torch.cuda.current_stream(dev).wait_event(ready)
-            a = RasterArgs()
-            a.n_cameras = C
+            a = _raster_args(C, width, height, 16, 7, 3, bg7, splats, b.flatten_ids, b.tile_offsets, b.tile_ends, render, alphas, last_ids)
             if KEEP_MASKS:
                 # the forward's rectangle-test ballots, one 64-bit word per (half tile, 64 list entries): the backward takes
                 # them instead of re-testing (and re-gathering) every list entry
                 stride = (b.flatten_ids.numel() >> 6) + C * b.tile_width * b.tile_height + 1
                 keep["masks"], keep["stride"] = torch.empty(2 * stride, dtype=torch.int64, device=dev), stride
                 a.keep_masks, a.keep_mask_stride = _ptr(keep["masks"]), stride
-            a.width, a.height, a.tile_size, a.D = width, height, 16, 7
-            a.splats, a.flatten_ids, a.tile_offsets = _ptr(splats), _ptr(b.flatten_ids), _ptr(b.tile_offsets)
-            a.tile_ends = _ptr(b.tile_ends)
-            a.background = _ptr(bg7)
-            a.ed_channel = 3
-            a.render, a.alphas, a.last_ids = _ptr(render), _ptr(alphas), _ptr(last_ids)
-            a.dn = ctypes.pointer(dn)
-            a.pair_counters = _ptr(counters)
+            a.dn, a.pair_counters = ctypes.pointer(dn), _ptr(counters)
             if fill["v_splats"] is not None:      # the backward's accumulation buffer, cleared by this launch on the way
                 a.zero_fill, a.zero_fill_bytes = _ptr(fill["v_splats"]), fill["v_splats"].numel() * 4
             _lib.run("dnsplat_raster_fwd", _lib.lib().dnsplat_raster_fwd, ctypes.byref(a), _stream())
 
-        b = bin_tiles(means2d.detach().reshape(-1, 2), radii.reshape(-1), depths.detach().reshape(-1), tiles.reshape(-1), width,
-                      height, 16, after_emit=composite, n_cameras=C, tight_splats=splats.detach() if tight else None,
-                      defer_ok=True, want_ends=True, tile_boxes=holder.get("tile_boxes") if holder is not None else None)
+        b = _bin_for(holder, composite, means2d, splats, depths, radii, tiles, width, height, 16, C, fused=True)
         for c in range(C):
             fx, fy, cx, cy = intr[c]
             _lib.run("dnsplat_dn_depth_normals", _lib.lib().dnsplat_dn_depth_normals, width, height, fx, fy, cx, cy,
                      _ptr(depth_raw[c]), _ptr(alphas[c]), _ptr(depth_max[c:]), _ptr(depth_out[c]), _ptr(surface_normal[c]), _stream())
-        if holder is not None:
-            holder["binning"] = b
         ctx.save_for_backward(means2d, splats, b.flatten_ids, b.tile_offsets, render, alphas, last_ids, bg_rgb)
         ctx.keep = keep
         ctx.binning = b
@@ -1145,28 +1193,14 @@ class _RasterDnFn(torch.autograd.Function):
         dn = DnPost()
         dn.background_rgb = _ptr(bg_rgb)
         dn.v_rgb, dn.v_depth, dn.v_normal, dn.v_accumulation = _ptr(v_rgb), _ptr(v_depth), _ptr(v_normal), _ptr(v_acc)
-        a = RasterArgs()
-        a.n_cameras = C
-        a.width, a.height, a.tile_size, a.D = width, height, 16, 7
-        a.splats, a.flatten_ids, a.tile_offsets = _ptr(splats), _ptr(flatten_ids), _ptr(tile_offsets)
-        a.tile_ends = _ptr(ctx.binning.tile_ends)
-        a.background = _ptr(_bg7(dev))
-        a.ed_channel = 3
-        a.render, a.alphas, a.last_ids = _ptr(render), _ptr(alphas), _ptr(last_ids)
-        a.xy_split = 4
-        a.v_splats = _ptr(v_splats)
-        a.dn = ctypes.pointer(dn)
-        a.pair_counters = _ptr(counters)
+        a = _raster_args(C, width, height, 16, 7, 3, _bg7(dev), splats, flatten_ids, tile_offsets, ctx.binning.tile_ends, render, alphas,
+                         last_ids)
+        a.xy_split, a.v_splats, a.dn, a.pair_counters = 4, _ptr(v_splats), ctypes.pointer(dn), _ptr(counters)
         if ctx.keep:
             a.keep_masks, a.keep_mask_stride = _ptr(ctx.keep["masks"]), ctx.keep["stride"]
         # "no visible opacity above the alpha cap in this frame" (written by the projection): lets the kernel drop the clamp handling
         a.saturation_flag = _ptr(ctx.saturation_flag) if SATURATION_FLAG else None
-        det = _det_begin(a, ctx.binning, dev) if counters is None else None
-        _lib.run("dnsplat_raster_bwd", _lib.lib().dnsplat_raster_bwd, ctypes.byref(a), _stream())
-        _det_finish(det, ctx.binning, v_splats)
-        if absgrad:
-            means2d.absgrad = v_splats[:, 14:16].reshape(means2d.shape)
-        return (_hand_over_means2d_grad(means2d, v_splats), v_splats) + none
+        return (_composite_bwd(a, ctx.binning, means2d, v_splats, absgrad, det=counters is None), v_splats) + none
 
 
 def rasterize_dn(means2d, splats, depths, radii, tiles, *, background_rgb, width, height, intrinsics, absgrad=True,
@@ -1177,12 +1211,8 @@ def rasterize_dn(means2d, splats, depths, radii, tiles, *, background_rgb, width
     instantiation (bench.py's VALU roofline)."""
     if isinstance(intrinsics[0], (int, float)):
         intrinsics = [tuple(intrinsics)]
-    if tight or tile_boxes is not None:    # ``tiles`` = tiles_bin (+ flag, + boxes): always taken together from the project() result
-        holder = {} if holder is None else holder
-        holder["tight"] = bool(tight)
-        holder["tile_boxes"] = tile_boxes
     return _RasterDnFn.apply(means2d, splats, depths, radii, tiles, background_rgb, width, height, list(intrinsics), absgrad,
-                             holder)
+                             _tile_boxes_into(holder, tight, tile_boxes))
 
 
 def camera_prepare(c2w: Tensor, fx: float, fy: float, cx: float, cy: float, with_normal_frame: bool = True, with_flag: bool = False,
