@@ -22,10 +22,13 @@ from .densify import DensifyStats  # noqa: F401
 from .install import install, install_losses, install_ssim, uninstall  # noqa: F401
 from .fused_loss import LocalPearsonDepthLoss, PearsonDepthLoss, local_pearson_depth, pearson_depth  # noqa: F401
 from .fused_loss import ags_mesh_loss_fused, ags_normal_loss  # noqa: F401
+from . import export  # noqa: F401
+from .export import OrientedPointCloud, export_oriented_points  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
     "DNSplatterRenderer", "RendererConfig", "Camera", "get_viewmat", "set_bin_policy", "set_deterministic", "set_grad_arena", "set_sh_exchange", "dp", "DensifyStats",
     "install", "install_losses", "install_ssim", "uninstall", "PearsonDepthLoss", "LocalPearsonDepthLoss", "pearson_depth",
-    "local_pearson_depth", "ags_normal_loss", "ags_mesh_loss_fused", "build_library", "load_library", "DnsplatError",
+    "local_pearson_depth", "ags_normal_loss", "ags_mesh_loss_fused", "export", "OrientedPointCloud",
+    "export_oriented_points", "build_library", "load_library", "DnsplatError",
 ]

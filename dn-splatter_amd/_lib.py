@@ -143,6 +143,16 @@ class PoseGrads(ctypes.Structure):
     _fields_ = [("partials", c_void_p), ("v_viewmat", c_void_p), ("c2w", c_void_p), ("v_c2w", c_void_p)]
 
 
+class BackprojectArgs(ctypes.Structure):
+    _fields_ = [
+        ("width", c_int32), ("height", c_int32),
+        ("depth", c_void_p), ("rgb", c_void_p), ("normal", c_void_p), ("mask", c_void_p), ("indices", c_void_p), ("counts", c_void_p),
+        ("n_rows", c_int32), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float),
+        ("xform", c_void_p), ("crop", c_void_p), ("points", c_void_p), ("colors", c_void_p), ("normals", c_void_p),
+        ("capacity", c_int64), ("state", c_void_p), ("scratch", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -160,6 +170,8 @@ EXPORTS = [
     "dnsplat_pearson_scratch_bytes", "dnsplat_pearson_depth",
     # likewise: the filtered normal loss of the AGS-Mesh strategy
     "dnsplat_ags_normal_scratch_bytes", "dnsplat_ags_normal_loss",
+    # likewise: the oriented point cloud of the mesh exporter
+    "dnsplat_pointcloud_scratch_bytes", "dnsplat_depth_edge_valid", "dnsplat_sample_valid_pixels", "dnsplat_backproject_points",
 ]
 
 _lib = None
@@ -240,9 +252,16 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_ags_normal_scratch_bytes.restype = c_size_t
         L.dnsplat_ags_normal_scratch_bytes.argtypes = [c_int32, c_int32]
         L.dnsplat_ags_normal_loss.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float] + [c_void_p] * 7
+        L.dnsplat_pointcloud_scratch_bytes.restype = c_size_t
+        L.dnsplat_pointcloud_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
+        L.dnsplat_depth_edge_valid.argtypes = [c_int32, c_int32, c_void_p, c_float, c_int32, c_void_p, c_void_p, c_void_p]
+        L.dnsplat_sample_valid_pixels.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]
+        L.dnsplat_backproject_points.argtypes = [ctypes.POINTER(BackprojectArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
-                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes"):
+                            "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
+                            "dnsplat_pointcloud_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

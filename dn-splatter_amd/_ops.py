@@ -12,7 +12,7 @@ dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rast
 get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
 
 One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
-``enqueue``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
+``enqueue``, ``_backproject_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BinArgs, Camera, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -335,6 +335,21 @@ def _camera_struct(viewmat, K, normal_frame, cfg: ProjCfg):
     c.antialiased = int(cfg.antialiased)
     c.tight_tiles = int(cfg.tight_tiles)
     return c
+
+
+def _backproject_args(width, height, depth, rgb, normal, mask, indices, counts, intrinsics, xform, crop, points, colors, normals,
+                      state, scratch):
+    a = BackprojectArgs()
+    a.width, a.height = width, height
+    a.depth, a.rgb, a.normal, a.mask = _ptr(depth), _ptr(rgb), _ptr(normal), _ptr(mask)
+    a.indices, a.counts = _ptr(indices), _ptr(counts)
+    a.n_rows = 0 if indices is None else indices.numel()
+    a.fx, a.fy, a.cx, a.cy = intrinsics
+    a.xform, a.crop = _ptr(xform), _ptr(crop)
+    a.points, a.colors, a.normals = _ptr(points), _ptr(colors), _ptr(normals if normal is not None else None)
+    a.capacity = points.shape[0]
+    a.state, a.scratch = _ptr(state), _ptr(scratch)
+    return a
 
 
 class _ShLayout:

@@ -54,7 +54,9 @@ extern "C" {
  * Entry points added after 15 are purely additive — new symbols and new structs, no existing struct or call changes — and are found
  * by symbol: the version stays 15 and the binding refuses a library that lacks one (dnsplat_pose_partial_rows,
  * dnsplat_project_bwd_pose / dnsplat_pose_grads: the camera pose gradient; dnsplat_pearson_depth / dnsplat_pearson_scratch_bytes: the
- * Pearson depth losses; dnsplat_ags_normal_loss / dnsplat_ags_normal_scratch_bytes: the filtered normal loss of the AGS-Mesh strategy). */
+ * Pearson depth losses; dnsplat_ags_normal_loss / dnsplat_ags_normal_scratch_bytes: the filtered normal loss of the AGS-Mesh strategy;
+ * dnsplat_depth_edge_valid / dnsplat_sample_valid_pixels / dnsplat_backproject_points / dnsplat_backproject_args /
+ * dnsplat_pointcloud_scratch_bytes: the oriented point cloud of the mesh exporter). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -528,6 +530,79 @@ size_t dnsplat_ags_normal_scratch_bytes(int32_t width, int32_t height);   /* 0 f
 int dnsplat_ags_normal_loss(int32_t width, int32_t height, const float *surf, const float *gt, const float *pred, int32_t layout,
                             int32_t mode, float weight, float *v_surf, float *v_pred, uint8_t *selection, void *scratch, double *sums,
                             int64_t *count, dnsplat_stream_t stream);
+
+/* Additive in ABI 15 (found by symbol).  The per-frame tail of the reference's `gs-mesh dn` exporter (export_mesh.py:351-476
+ * DepthAndNormalMapsPoisson; the `tsdf` exporter :824-927 back-projects the same way): an oriented, coloured point cloud from the
+ * rendered depth, colour and surface-normal images of a camera.  Three calls that share one caller-owned scratch of
+ * dnsplat_pointcloud_scratch_bytes(width, height, k) bytes (16-byte aligned; its contents need not survive from one call to the next).
+ * None allocates, synchronises or uses an atomic; equal inputs (and seed) give equal bits.  A frame holds at most 2^31 - 1 pixels
+ * (DNSPLAT_ERR_UNSUPPORTED beyond); NULL required pointers and non-positive sizes return DNSPLAT_ERR_INVALID_ARG; both without a launch.
+ *
+ * dnsplat_depth_edge_valid — find_depth_edges(depth, threshold, dilation_itr) < 0.2 (export_mesh.py:58-90, :379-386), two launches.
+ *   inv = 1 / (depth + 1e-6) in IEEE fp32, lap = ((up + down) + left) + right - 4 inv with ZERO taps outside the frame (the reference's
+ *   padding=1), edge = lap > threshold (a nan Laplacian is no edge), valid = no edge pixel within Chebyshev distance dilation_itr —
+ *   what dilation_itr rounds of the 3 x 3 all-ones conv2d followed by `> 0` compute on a 0/1 map.  The threshold decisions travel as one
+ *   64-bit word per 64 pixels of a row; a workgroup dilates DNSPLAT_EDGE_ROW_TILE rows x 8 words.
+ *   depth [H,W] fp32; valid [H,W] bytes (torch.bool) out.  0 <= dilation_itr <= DNSPLAT_EDGE_MAX_DILATION, else DNSPLAT_ERR_UNSUPPORTED.
+ *
+ * dnsplat_sample_valid_pixels — pick_indices_at_random (export_mesh.py:50-55) without the nonzero / randperm round trip: m = min(k, n)
+ *   of the n valid pixels, uniformly and without replacement; n never reaches the host.  Four launches.
+ *   valid      [H,W] bytes, or NULL: then a pixel is valid iff !(depth == 0) — torch.nonzero of the depth image, the reference's
+ *              `valid_mask = depth_map`; a nan depth is valid.  One of valid / depth must be given (valid wins).
+ *   indices    out, int32 [k] (may be NULL for k == 0): rows [0, m) hold flat pixel indices y * width + x, rows [m, k) hold -1.
+ *   counts     out, device int32 [2] = {n, m}.
+ *   n <= k: all valid pixels in ascending order (the reference's behaviour).  n > k: indices[t] = compact[pi(t)], compact the ascending
+ *   list of the valid pixels and pi a bijection of [0, n) keyed by `seed` (a kernel argument, no device state):
+ *     bits = ceil(log2 n) (0 for n = 1), half = max(1, ceil(bits / 2)), mask = 2^half - 1; a balanced Feistel network on 2 half bits with
+ *     DNSPLAT_SAMPLE_ROUNDS = 4 rounds  (L, R) <- (R, L ^ (mix32(R ^ key_r) & mask)),  x = L << half | R, starting from x = t, repeated
+ *     while x >= n (cycle walking);  key_r = mix32(lo32(seed) ^ mix32(hi32(seed) + 0x9e3779b9 (r + 1))), r = 0 .. 3;
+ *     mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (all in uint32).
+ *   This is the reference's DISTRIBUTION from another stream: its draw is torch.randperm on the CPU generator, which needs n on the host.
+ *   A caller who wants that very draw passes its own indices to dnsplat_backproject_points.
+ *
+ * dnsplat_backproject_points — get_colored_points_from_depth (utils/camera_utils.py:92-210) with the normal-map transform
+ *   (export_mesh.py:411-428) and the crop (:462-468) for the selected pixels only; three launches.  One thread per row j of `indices`
+ *   (rows [0, counts[1]) when counts is given, else all n_rows; indices == NULL: every pixel in raster order, the tsdf exporter's call):
+ *     d = mask && !mask[i] ? 0 : depth[i]            the mask does not change which pixels were selected (:391-396)
+ *     p = ((u + 0.5 - cx) * d / fx, (v + 0.5 - cy) * d / fy, d)            in that order of operations
+ *     world_j = ((p_0 A_0j + p_1 A_1j) + p_2 A_2j) + t_j                   A = inverse of the OpenCV camera-to-world rotation, row-major
+ *     color = rgb[i], bit for bit
+ *     normal = R normalize(diag(1, -1, -1) (2 s - 1)),  normalize(x) = x / max(|x|, 1e-12): a stored (0.5, 0.5, 0.5) gives exactly 0
+ *     kept iff |B_k0 w_0 + B_k1 w_1 + B_k2 w_2 + B_k3| < h_k for k = 0, 1, 2 (strict) when a crop box is given
+ *   Kept rows are appended in the order of `indices` to points / colors / normals at the device cursor state[0], which moves by their
+ *   number but not past capacity; a row that would land at or beyond capacity is not written and state[1] is set to 1.  An index outside
+ *   [0, width * height) is dropped and sets state[2] to 1.  The caller zeroes state once.
+ *   xform   DEVICE, 21 floats: A[9], t[3], R[9] (R the camera-to-world rotation itself) — on the device so that a pose that lives there
+ *           never passes through the host.    crop   DEVICE, 15 floats: B[12] (world -> box, 3 x 4 row-major), h[3]; or NULL.
+ *   normal / normals NULL together: no normals are written. */
+#define DNSPLAT_EDGE_ROW_TILE 32
+#define DNSPLAT_EDGE_MAX_DILATION 64
+#define DNSPLAT_SAMPLE_ROUNDS 4
+typedef struct dnsplat_backproject_args {
+    int32_t width, height;
+    const float *depth;      /* [H,W] */
+    const float *rgb;        /* [H,W,3] */
+    const float *normal;     /* [H,W,3] in [0, 1] (outputs["surface_normal"]) or NULL */
+    const uint8_t *mask;     /* [H,W] bytes or NULL */
+    const int32_t *indices;  /* [n_rows] flat pixel indices or NULL */
+    const int32_t *counts;   /* device {n, m} of dnsplat_sample_valid_pixels or NULL */
+    int32_t n_rows;          /* length of indices; ignored without indices */
+    float fx, fy, cx, cy;
+    const float *xform;      /* device [21] */
+    const float *crop;       /* device [15] or NULL */
+    float *points;           /* [capacity,3] */
+    float *colors;           /* [capacity,3] */
+    float *normals;          /* [capacity,3] or NULL */
+    int64_t capacity;
+    int64_t *state;          /* device int64 [3]: cursor, overflow, index out of range */
+    void *scratch;
+} dnsplat_backproject_args;
+size_t dnsplat_pointcloud_scratch_bytes(int32_t width, int32_t height, int32_t k);   /* 0 for an invalid or unsupported size */
+int dnsplat_depth_edge_valid(int32_t width, int32_t height, const float *depth, float threshold, int32_t dilation_itr, uint8_t *valid,
+                             void *scratch, dnsplat_stream_t stream);
+int dnsplat_sample_valid_pixels(int32_t width, int32_t height, const uint8_t *valid, const float *depth, int32_t k, uint64_t seed,
+                                int32_t *indices, int32_t *counts, void *scratch, dnsplat_stream_t stream);
+int dnsplat_backproject_points(const dnsplat_backproject_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
