@@ -19,16 +19,19 @@ from .model import Camera, DNSplatterRenderer, RendererConfig, get_viewmat  # no
 from ._ops import set_bin_policy, set_deterministic, set_grad_arena, set_sh_exchange  # noqa: F401
 from . import dp  # noqa: F401
 from .densify import DensifyStats  # noqa: F401
-from .install import install, install_losses, install_ssim, uninstall  # noqa: F401
+from .install import install, install_losses, install_metrics, install_ssim, uninstall  # noqa: F401
 from .fused_loss import LocalPearsonDepthLoss, PearsonDepthLoss, local_pearson_depth, pearson_depth  # noqa: F401
 from .fused_loss import ags_mesh_loss_fused, ags_normal_loss  # noqa: F401
+from . import fused_metrics, torch_metrics  # noqa: F401
+from .fused_metrics import image_metrics, image_metrics_dict  # noqa: F401
 from . import export  # noqa: F401
 from .export import OrientedPointCloud, export_oriented_points  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
     "DNSplatterRenderer", "RendererConfig", "Camera", "get_viewmat", "set_bin_policy", "set_deterministic", "set_grad_arena", "set_sh_exchange", "dp", "DensifyStats",
-    "install", "install_losses", "install_ssim", "uninstall", "PearsonDepthLoss", "LocalPearsonDepthLoss", "pearson_depth",
+    "install", "install_losses", "install_metrics", "install_ssim", "uninstall", "image_metrics", "image_metrics_dict",
+    "fused_metrics", "torch_metrics", "PearsonDepthLoss", "LocalPearsonDepthLoss", "pearson_depth",
     "local_pearson_depth", "ags_normal_loss", "ags_mesh_loss_fused", "export", "OrientedPointCloud",
     "export_oriented_points", "build_library", "load_library", "DnsplatError",
 ]

@@ -153,6 +153,16 @@ class BackprojectArgs(ctypes.Structure):
     ]
 
 
+class EvalMetricsArgs(ctypes.Structure):
+    _fields_ = [
+        ("width", c_int32), ("height", c_int32),
+        ("rgb", c_void_p), ("gt_rgb", c_void_p), ("depth", c_void_p), ("gt_depth", c_void_p),
+        ("depth_tolerance", c_float), ("normal_layout", c_int32),
+        ("normal", c_void_p), ("gt_normal", c_void_p),
+        ("scratch", c_void_p), ("metrics", c_void_p), ("counts", c_void_p), ("sums", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -172,6 +182,8 @@ EXPORTS = [
     "dnsplat_ags_normal_scratch_bytes", "dnsplat_ags_normal_loss",
     # likewise: the oriented point cloud of the mesh exporter
     "dnsplat_pointcloud_scratch_bytes", "dnsplat_depth_edge_valid", "dnsplat_sample_valid_pixels", "dnsplat_backproject_points",
+    # likewise: the evaluation scores (depth, normal, mse / psnr)
+    "dnsplat_eval_metrics_scratch_bytes", "dnsplat_eval_metrics",
 ]
 
 _lib = None
@@ -258,10 +270,13 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_sample_valid_pixels.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p,
                                                   c_void_p]
         L.dnsplat_backproject_points.argtypes = [ctypes.POINTER(BackprojectArgs), c_void_p]
+        L.dnsplat_eval_metrics_scratch_bytes.restype = c_size_t
+        L.dnsplat_eval_metrics_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_eval_metrics.argtypes = [ctypes.POINTER(EvalMetricsArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
-                            "dnsplat_pointcloud_scratch_bytes"):
+                            "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

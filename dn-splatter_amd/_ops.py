@@ -12,7 +12,7 @@ dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rast
 get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
 
 One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
-``enqueue``, ``_backproject_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
+``enqueue``, ``_backproject_args``, ``_eval_metrics_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, EvalMetricsArgs, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -349,6 +349,17 @@ def _backproject_args(width, height, depth, rgb, normal, mask, indices, counts, 
     a.points, a.colors, a.normals = _ptr(points), _ptr(colors), _ptr(normals if normal is not None else None)
     a.capacity = points.shape[0]
     a.state, a.scratch = _ptr(state), _ptr(scratch)
+    return a
+
+
+def _eval_metrics_args(width, height, rgb, gt_rgb, depth, gt_depth, depth_tolerance, normal, gt_normal, normal_layout, scratch,
+                       metrics, counts, sums):
+    a = EvalMetricsArgs()
+    a.width, a.height = width, height
+    a.rgb, a.gt_rgb, a.depth, a.gt_depth = _ptr(rgb), _ptr(gt_rgb), _ptr(depth), _ptr(gt_depth)
+    a.depth_tolerance, a.normal_layout = depth_tolerance, normal_layout
+    a.normal, a.gt_normal = _ptr(normal), _ptr(gt_normal)
+    a.scratch, a.metrics, a.counts, a.sums = _ptr(scratch), _ptr(metrics), _ptr(counts), _ptr(sums)
     return a
 
 

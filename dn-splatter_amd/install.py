@@ -209,6 +209,34 @@ def install_losses(model):
     return swapped
 
 
+def install_metrics(model):
+    """Swaps the three scoring modules ``DNSplatterModel`` holds (dn_model.py:176-187) for their HIP drop-ins of ``fused_metrics``, when
+    they are the ones the reference constructs — by class NAME: ``model.depth_metrics`` (``DepthMetrics`` -> ``fused_metrics.DepthMetrics``
+    with the same tolerance), ``model.normal_metrics`` (``NormalMetrics``) and ``model.psnr`` (torchmetrics' ``PeakSignalNoiseRatio`` ->
+    ``fused_metrics.PSNR``); also ``install_ssim(model)``.  ``get_image_metrics_and_images`` and ``get_metrics_dict`` then run the
+    reference's own text over ``dnsplat_eval_metrics``.  Each original is kept as ``model._dnsplat_original_<name>``.  ``rgb_metrics``
+    and ``lpips`` (a network) are left alone.  Idempotent; returns the list of what was swapped."""
+    from . import fused_metrics
+
+    swapped = []
+    for name, cls_name, make in (("depth_metrics", "DepthMetrics", lambda old: fused_metrics.DepthMetrics(getattr(old, "tolerance", 0.1))),
+                                 ("normal_metrics", "NormalMetrics", lambda old: fused_metrics.NormalMetrics()),
+                                 ("psnr", "PeakSignalNoiseRatio", lambda old: fused_metrics.PSNR())):
+        old = getattr(model, name, None)
+        if old is None or type(old).__name__ != cls_name or type(old).__module__ == fused_metrics.__name__:
+            continue
+        object.__setattr__(model, "_dnsplat_original_" + name, old)
+        setattr(model, name, make(old))
+        swapped.append(name)
+    if hasattr(model, "ssim"):
+        from .fused_loss import SSIM
+
+        if not isinstance(model.ssim, SSIM):
+            install_ssim(model)
+            swapped.append("ssim")
+    return swapped
+
+
 def uninstall(model_cls):
     """Puts the original ``get_outputs`` back."""
     original = model_cls.__dict__.get(_ORIGINAL)

@@ -56,7 +56,8 @@ extern "C" {
  * dnsplat_project_bwd_pose / dnsplat_pose_grads: the camera pose gradient; dnsplat_pearson_depth / dnsplat_pearson_scratch_bytes: the
  * Pearson depth losses; dnsplat_ags_normal_loss / dnsplat_ags_normal_scratch_bytes: the filtered normal loss of the AGS-Mesh strategy;
  * dnsplat_depth_edge_valid / dnsplat_sample_valid_pixels / dnsplat_backproject_points / dnsplat_backproject_args /
- * dnsplat_pointcloud_scratch_bytes: the oriented point cloud of the mesh exporter). */
+ * dnsplat_pointcloud_scratch_bytes: the oriented point cloud of the mesh exporter; dnsplat_eval_metrics / dnsplat_eval_metrics_args /
+ * dnsplat_eval_metrics_scratch_bytes: the evaluation scores). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -603,6 +604,85 @@ int dnsplat_depth_edge_valid(int32_t width, int32_t height, const float *depth, 
 int dnsplat_sample_valid_pixels(int32_t width, int32_t height, const uint8_t *valid, const float *depth, int32_t k, uint64_t seed,
                                 int32_t *indices, int32_t *counts, void *scratch, dnsplat_stream_t stream);
 int dnsplat_backproject_points(const dnsplat_backproject_args *args, dnsplat_stream_t stream);
+
+/* Additive in ABI 15 (found by symbol).  The evaluation scores of one frame — DNSplatterModel.get_image_metrics_and_images
+ * (dn_model.py:809-926) and get_metrics_dict (:731-807): DepthMetrics.forward (metrics.py:130-149), NormalMetrics.forward (:171-183)
+ * with mean_angular_error (:59-74), and the mse / psnr of torchmetrics' PeakSignalNoiseRatio(data_range=1.0) — in one call that reads
+ * each given image once (plus the two normal images twice more for the median), where the reference runs about twenty boolean-mask
+ * gathers (a host synchronisation each), a sort-based torch.median over 3 H W values and fourteen .item() reads.  SSIM is
+ * dnsplat_ssim; LPIPS (a network) is not part of this library.
+ * Three optional image PAIRS, fp32; both pointers of a pair are NULL or neither is, and at least one pair is given:
+ *   rgb, gt_rgb         [H,W,3].  mse = mean over 3 H W of (gt - pred)^2, psnr = 10 log10(1 / mse) (mse == 0: inf).  The mse -> psnr
+ *                       formula is torchmetrics' as published; torchmetrics itself was not at hand: PARITY UNPINNED.
+ *   depth, gt_depth     [H,W], with depth_tolerance.  Over the pixels with gt > depth_tolerance (fp32; a nan is not above it):
+ *                       t = max(gt / pred, pred / gt), two IEEE fp32 divisions; a1 / a2 / a3 = the share with t < 1.25, < 1.5625,
+ *                       < 1.953125; rmse = sqrt(mean (gt - pred)^2); rmse_log = the mean over the NON-NAN terms of
+ *                       sqrt((log gt - log pred)^2) — a mean absolute log difference, as the reference writes it under that name;
+ *                       abs_rel = mean |gt - pred| / gt; sq_rel = mean (gt - pred)^2 / gt.  Plain IEEE: a nan t is below no
+ *                       threshold; pred == 0 gives t = inf and rmse_log = inf; a NEGATIVE pred gives a negative t, which is below
+ *                       all three thresholds, and a nan log term that is dropped; no pixel above the tolerance gives nan everywhere.
+ *   normal, gt_normal   three channels, normal_layout as DNSPLAT_AGS_LAYOUT_*: HWC = [H,W,3] (what outputs / batch hold), CHW = [3,H,W]
+ *                       (a contiguous copy of what the module receives).  Values are taken AS THEY ARE, in [0, 1]: the reference applies
+ *                       no 2 x - 1 here.  mae = mean over the pixels of acos(clamp(dot, -1, 1)), dot = (g0 p0 + g1 p1) + g2 p2 in fp32;
+ *                       rmse = sqrt(mean over 3 H W of (g - p)^2); mean_err = mean |g - p|; med_err = torch.median of the 3 H W values
+ *                       |g - p|: the LOWER median, the element of rank (n - 1) / 2 of the sorted values, with inf sorting as a value
+ *                       and nan if any value is nan.  It is the bit pattern of one of the differences: exact.
+ *   metrics    out, device float [DNSPLAT_METRIC_COUNT], at the DNSPLAT_METRIC_* indices; the entries of an absent pair are nan, the
+ *              unused tail is 0.  Sums in double, the divisions, square roots and log10 in double, rounded once.
+ *   counts     out, device int64 [DNSPLAT_METRIC_COUNTS], at the DNSPLAT_METRIC_N_* indices (0 for an absent pair).
+ *   sums       out or NULL, device double [DNSPLAT_METRIC_SUMS]: the numerators before any division, at DNSPLAT_METRIC_SUM_*.
+ *   scratch    dnsplat_eval_metrics_scratch_bytes(width, height) bytes, 8-byte aligned.  No precondition on its contents (the call
+ *              zeroes what it accumulates into), and they need not survive.
+ * One partial per workgroup (sums in double, counts as integers) added in a fixed order; the median is a radix selection on the 31
+ * value bits of |g - p| in three integer histogram rounds (11 + 11 + 9 bits); no floating-point atomic: the result is
+ * bit-reproducible.  Up to seven launches, no allocation, no synchronisation; nothing is read on the host between the rounds.
+ * Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL args / scratch / metrics / counts, width < 1, height < 1, half a pair, all
+ * three pairs absent, or a normal pair with a layout other than the two above; DNSPLAT_ERR_UNSUPPORTED for more than 2^31 - 1 pixels. */
+#define DNSPLAT_METRIC_RGB_MSE 0
+#define DNSPLAT_METRIC_RGB_PSNR 1
+#define DNSPLAT_METRIC_DEPTH_ABS_REL 2
+#define DNSPLAT_METRIC_DEPTH_SQ_REL 3
+#define DNSPLAT_METRIC_DEPTH_RMSE 4
+#define DNSPLAT_METRIC_DEPTH_RMSE_LOG 5
+#define DNSPLAT_METRIC_DEPTH_A1 6
+#define DNSPLAT_METRIC_DEPTH_A2 7
+#define DNSPLAT_METRIC_DEPTH_A3 8
+#define DNSPLAT_METRIC_NORMAL_MAE 9
+#define DNSPLAT_METRIC_NORMAL_RMSE 10
+#define DNSPLAT_METRIC_NORMAL_MEAN_ERR 11
+#define DNSPLAT_METRIC_NORMAL_MED_ERR 12
+#define DNSPLAT_METRIC_USED 13
+#define DNSPLAT_METRIC_COUNT 16
+#define DNSPLAT_METRIC_N_DEPTH_MASKED 0    /* pixels with gt > depth_tolerance */
+#define DNSPLAT_METRIC_N_DEPTH_A1 1        /* of them, t < 1.25 */
+#define DNSPLAT_METRIC_N_DEPTH_A2 2        /* t < 1.5625 */
+#define DNSPLAT_METRIC_N_DEPTH_A3 3        /* t < 1.953125 */
+#define DNSPLAT_METRIC_N_DEPTH_LOG 4       /* non-nan log terms */
+#define DNSPLAT_METRIC_N_NORMAL_NAN 5      /* nan values among the 3 H W differences |g - p| */
+#define DNSPLAT_METRIC_COUNTS 8
+#define DNSPLAT_METRIC_SUM_RGB_SQ 0           /* sum over 3 H W of (gt - pred)^2 */
+#define DNSPLAT_METRIC_SUM_DEPTH_SQ 1         /* over the masked pixels: (gt - pred)^2 */
+#define DNSPLAT_METRIC_SUM_DEPTH_ABS_REL 2    /* |gt - pred| / gt */
+#define DNSPLAT_METRIC_SUM_DEPTH_SQ_REL 3     /* (gt - pred)^2 / gt */
+#define DNSPLAT_METRIC_SUM_DEPTH_LOG 4        /* |log gt - log pred| where it is not nan */
+#define DNSPLAT_METRIC_SUM_NORMAL_ANGLE 5     /* over the pixels: acos(clamp(dot, -1, 1)) */
+#define DNSPLAT_METRIC_SUM_NORMAL_SQ 6        /* over 3 H W: (g - p)^2 */
+#define DNSPLAT_METRIC_SUM_NORMAL_ABS 7       /* |g - p| */
+#define DNSPLAT_METRIC_SUMS 8
+typedef struct dnsplat_eval_metrics_args {
+    int32_t width, height;
+    const float *rgb, *gt_rgb;          /* [H,W,3] or both NULL */
+    const float *depth, *gt_depth;      /* [H,W] or both NULL */
+    float depth_tolerance;
+    int32_t normal_layout;              /* DNSPLAT_AGS_LAYOUT_*; looked at only with a normal pair */
+    const float *normal, *gt_normal;    /* three channels in that layout, or both NULL */
+    void *scratch;
+    float *metrics;                     /* device [DNSPLAT_METRIC_COUNT] */
+    int64_t *counts;                    /* device [DNSPLAT_METRIC_COUNTS] */
+    double *sums;                       /* device [DNSPLAT_METRIC_SUMS] or NULL */
+} dnsplat_eval_metrics_args;
+size_t dnsplat_eval_metrics_scratch_bytes(int32_t width, int32_t height);   /* 0 for an invalid size */
+int dnsplat_eval_metrics(const dnsplat_eval_metrics_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
