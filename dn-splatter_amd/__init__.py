@@ -26,6 +26,8 @@ from . import fused_metrics, torch_metrics  # noqa: F401
 from .fused_metrics import image_metrics, image_metrics_dict  # noqa: F401
 from . import export  # noqa: F401
 from .export import OrientedPointCloud, export_oriented_points  # noqa: F401
+from . import density, torch_density  # noqa: F401
+from .density import GaussianDensityField, build_index, density_volume, install_density, knn  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -33,5 +35,6 @@ __all__ = [
     "install", "install_losses", "install_metrics", "install_ssim", "uninstall", "image_metrics", "image_metrics_dict",
     "fused_metrics", "torch_metrics", "PearsonDepthLoss", "LocalPearsonDepthLoss", "pearson_depth",
     "local_pearson_depth", "ags_normal_loss", "ags_mesh_loss_fused", "export", "OrientedPointCloud",
-    "export_oriented_points", "build_library", "load_library", "DnsplatError",
+    "export_oriented_points", "density", "torch_density", "GaussianDensityField", "build_index", "density_volume", "install_density", "knn",
+    "build_library", "load_library", "DnsplatError",
 ]

@@ -163,6 +163,15 @@ class EvalMetricsArgs(ctypes.Structure):
     ]
 
 
+class DensityArgs(ctypes.Structure):
+    _fields_ = [
+        ("N", c_int32), ("index", c_void_p), ("records", c_void_p), ("M", c_int64), ("samples", c_void_p),
+        ("X", c_void_p), ("Y", c_void_p), ("Z", c_void_p), ("Rx", c_int32), ("Ry", c_int32), ("Rz", c_int32),
+        ("mask", c_void_p), ("fill", c_float), ("neighbors", c_void_p), ("neighbors_int64", c_int32),
+        ("k", c_int32), ("skip", c_int32), ("num_closest", c_int32), ("density", c_void_p), ("normals", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -184,6 +193,9 @@ EXPORTS = [
     "dnsplat_pointcloud_scratch_bytes", "dnsplat_depth_edge_valid", "dnsplat_sample_valid_pixels", "dnsplat_backproject_points",
     # likewise: the evaluation scores (depth, normal, mse / psnr)
     "dnsplat_eval_metrics_scratch_bytes", "dnsplat_eval_metrics",
+    # likewise: the Gaussian density field (exact k-NN, density, normals, volume)
+    "dnsplat_knn_grid_dim", "dnsplat_knn_index_bytes", "dnsplat_knn_build", "dnsplat_knn_query", "dnsplat_density_pack",
+    "dnsplat_density_eval",
 ]
 
 _lib = None
@@ -273,10 +285,19 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_eval_metrics_scratch_bytes.restype = c_size_t
         L.dnsplat_eval_metrics_scratch_bytes.argtypes = [c_int32, c_int32]
         L.dnsplat_eval_metrics.argtypes = [ctypes.POINTER(EvalMetricsArgs), c_void_p]
+        L.dnsplat_knn_grid_dim.restype = c_int32
+        L.dnsplat_knn_grid_dim.argtypes = [c_int32]
+        L.dnsplat_knn_index_bytes.restype = c_size_t
+        L.dnsplat_knn_index_bytes.argtypes = [c_int32]
+        L.dnsplat_knn_build.argtypes = [c_int32, c_void_p, c_void_p, c_void_p]
+        L.dnsplat_knn_query.argtypes = [c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+        L.dnsplat_density_pack.argtypes = [c_int32] + [c_void_p] * 6
+        L.dnsplat_density_eval.argtypes = [ctypes.POINTER(DensityArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
-                            "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes"):
+                            "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
+                            "dnsplat_knn_index_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

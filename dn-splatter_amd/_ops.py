@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, EvalMetricsArgs, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, DensityArgs, EvalMetricsArgs, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -360,6 +360,23 @@ def _eval_metrics_args(width, height, rgb, gt_rgb, depth, gt_depth, depth_tolera
     a.depth_tolerance, a.normal_layout = depth_tolerance, normal_layout
     a.normal, a.gt_normal = _ptr(normal), _ptr(gt_normal)
     a.scratch, a.metrics, a.counts, a.sums = _ptr(scratch), _ptr(metrics), _ptr(counts), _ptr(sums)
+    return a
+
+
+def _density_args(N, index, records, samples, lattice, mask, fill, neighbors, k, skip, num_closest, density, normals):
+    """``lattice``: None, or the three coordinate arrays (X, Y, Z) that replace ``samples``."""
+    a = DensityArgs()
+    a.N, a.index, a.records = N, _ptr(index), _ptr(records)
+    a.M, a.samples = (0, None) if samples is None else (samples.shape[0], _ptr(samples))
+    if lattice is not None:
+        X, Y, Z = lattice
+        a.X, a.Y, a.Z = _ptr(X), _ptr(Y), _ptr(Z)
+        a.Rx, a.Ry, a.Rz = X.numel(), Y.numel(), Z.numel()
+    a.mask, a.fill = _ptr(mask), fill
+    a.neighbors = _ptr(neighbors)
+    a.neighbors_int64 = int(neighbors is not None and neighbors.dtype == torch.int64)
+    a.k, a.skip, a.num_closest = k, skip, num_closest
+    a.density, a.normals = _ptr(density), _ptr(normals)
     return a
 
 

@@ -26,7 +26,7 @@ from torch import Tensor
 from . import _lib
 from ._lib import DnsplatError
 from ._ops import _backproject_args, _f32c, _need_gpu, _ptr, _stream
-from .torch_export import box_to_world
+from .torch_export import box_to_world, camera_points
 
 EDGE_ROW_TILE = 32          # include/dnsplat.h DNSPLAT_EDGE_ROW_TILE: rows a workgroup of the dilation kernel finishes
 EDGE_MAX_DILATION = 64      # DNSPLAT_EDGE_MAX_DILATION
@@ -215,6 +215,35 @@ def get_colored_points_from_depth(depths: Tensor, rgbs: Tensor, c2w: Tensor, fx:
     return points[:rows], colors[:rows]
 
 
+def density_grad_samples(depth: Tensor, camera, c2w_cv: Tensor) -> Tensor:
+    """export_mesh.py:431-441: every pixel of ``depth`` [H,W] back-projected at 0.99 of its depth, [H W, 3] on the device."""
+    H, W = depth.shape
+    c2w = c2w_cv.to(device=depth.device, dtype=torch.float32)
+    A = torch.linalg.inv_ex(c2w[:3, :3])[0]
+    return camera_points(depth * 0.99, camera.fx, camera.fy, camera.cx, camera.cy, (W, H)) @ A + c2w[:3, 3]
+
+
+def density_grad_normal_image(field, depth: Tensor, camera, c2w_cv: Tensor) -> Tensor:
+    """The ``density_grad`` branch of the exporter (export_mesh.py:430-457) as an image the back-projection kernel takes in place of
+    ``outputs["surface_normal"]``: ``field.density_grad(..., num_closest_gaussians=1)`` at ``density_grad_samples`` (the second-nearest
+    Gaussian, as ``knn_sk`` has it), flipped towards the camera, times the camera rotation and diag(1, -1, -1), normalised — the
+    vector t the branch computes.  The kernel applies R normalize(diag(1, -1, -1) (2 s - 1)) to a stored s, so the image holds
+    s = (diag(1, -1, -1) Rᵀ t + 1) / 2 and the appended normal is t to fp32 rounding.  [H,W,3] float32; the search and the gradient
+    run in ``dnsplat_density_eval``, the elementwise frame around them in torch on the device.  No host synchronisation."""
+    H, W = depth.shape
+    c2w = c2w_cv.to(device=depth.device, dtype=torch.float32)
+    R, t = c2w[:3, :3], c2w[:3, 3]
+    xyz = density_grad_samples(depth, camera, c2w)
+    n = field.density_grad(xyz, num_closest_gaussians=1)
+    view = t - xyz
+    view = view / view.norm(dim=-1, keepdim=True)
+    n = torch.where(((n * view).sum(-1) < 0)[:, None], -n, n)
+    flip = torch.cat([torch.ones_like(t[:1]), -torch.ones_like(t[:2])])          # diag(1, -1, -1) without host data
+    n = (n @ R) * flip
+    n = n / n.norm(dim=-1, keepdim=True)
+    return (((n @ R) * flip + 1) / 2).reshape(H, W, 3)
+
+
 # ---- the exporter's loop ---------------------------------------------------------------------------------------------------------------
 
 
@@ -251,8 +280,8 @@ class OrientedPointCloud:
 
     def add_frame(self, outputs, camera, *, samples_per_frame: int, filter_edges: bool = False, edge_threshold: float = 0.004,
                   edge_dilation_iterations: int = 10, mask: Optional[Tensor] = None, indices: Optional[Tensor] = None, crop_box=None,
-                  seed: int = 0) -> None:
-        """One trip of the loop at export_mesh.py:360-472 (``normal_method == "normal_maps"``) for the ``outputs`` of ``camera`` (a
+                  seed: int = 0, normal_method: str = "normal_maps", field=None) -> None:
+        """One trip of the loop at export_mesh.py:360-472 for the ``outputs`` of ``camera`` (a
         ``model.Camera``): pick ``samples_per_frame`` of the valid pixels (off the dilated depth edges if ``filter_edges``, else with a
         nonzero depth), back-project them with ``camera_to_worlds · diag(1, -1, -1, 1)`` (:370-375), take their colours and world
         normals, keep those inside ``crop_box``, append.  ``mask`` (bool [H,W]) zeroes the depth of the pixels outside it AFTER the
@@ -260,7 +289,16 @@ class OrientedPointCloud:
         ``crop_box``: anything with nerfstudio's ``OrientedBox`` attributes ``R`` [3,3], ``T`` [3], ``S`` [3]; a point is kept iff every
         coordinate of inverse(pose)·[p; 1] lies strictly inside ±S / 2 — ``OrientedBox.within`` restated from memory (nerfstudio is not
         a dependency): "parity unpinned", like the compositing rules.  Frames that contribute nothing (no valid pixel, nothing inside
-        the box) simply append nothing, where the reference ``continue``s.  No host synchronisation."""
+        the box) simply append nothing, where the reference ``continue``s.  No host synchronisation.
+
+        ``normal_method="density_grad"`` with ``field`` (a ``density.GaussianDensityField``) takes the normals from the density field
+        instead of ``outputs["surface_normal"]`` (:430-457, ``density_grad_normal_image``).  The reference computes exactly this and
+        then overwrites it with the rendered normal map at :459, so its two methods export the same normals; here the branch keeps what
+        it computed — its documented intent.  The default, ``"normal_maps"``, is unchanged."""
+        if normal_method not in ("normal_maps", "density_grad"):
+            raise ValueError(f"normal_method must be 'normal_maps' or 'density_grad', got {normal_method!r}")
+        if normal_method == "density_grad" and field is None:
+            raise ValueError("normal_method='density_grad' needs field=GaussianDensityField(...)")
         if samples_per_frame < 0:
             raise ValueError(f"samples_per_frame must be >= 0, got {samples_per_frame}")
         depth = _f32c(_image2d(outputs["depth"], "depth"), "depth")
@@ -275,8 +313,9 @@ class OrientedPointCloud:
         else:
             scratch = self._scratch_for(W, H, int(indices.numel()))
         c2w = _export_c2w(camera.camera_to_worlds)
+        surface_normal = outputs["surface_normal"] if normal_method == "normal_maps" else density_grad_normal_image(field, depth, camera, c2w)
         backproject_points(depth, outputs["rgb"], c2w, camera.fx, camera.fy, camera.cx, camera.cy, points=self.points, colors=self.colors,
-                           normals=self.normals, state=self.state, surface_normal=outputs["surface_normal"], mask=mask, indices=indices,
+                           normals=self.normals, state=self.state, surface_normal=surface_normal, mask=mask, indices=indices,
                            counts=counts, crop_box=crop_box, scratch=scratch)
 
     def finish(self) -> Tuple[Tensor, Tensor, Tensor]:

@@ -9,7 +9,8 @@ Scale initialisation: the reference runs sklearn's kd-tree kNN on the CPU (inher
 ``k_nearest_sklearn``).  ``scale_init="knn"`` does exactly that; ``scale_init="closed_form"``
 (default above 100k points) uses the expectation of the same quantity for a uniform Poisson
 process of the same density, E[(d1+d2+d3)/3] = 1.15747 * (3 / (4 pi rho))^(1/3), identical for every
-point — documented in DESIGN.md, and what bench.py reports in its config.
+point — documented in DESIGN.md, and what bench.py reports in its config.  ``scale_init="knn_hip"`` is the same 3-NN mean through
+``density.knn(means, means, 3, skip=1)`` on the device (any N; the distances are the float64 ones rounded to float32).
 
 Cameras (builder-chosen, the reference hard-codes none): pinhole, principal point at the image
 centre, radius-8 orbit around the origin in the x-z plane looking at the origin, +y up,
@@ -56,6 +57,12 @@ def make_gauss_params(N: int, sh_degree: int = 3, seed: int = 0, sh_rest_std: fl
         nn_model = NearestNeighbors(n_neighbors=4, algorithm="auto", metric="euclidean").fit(means.numpy())
         distances, _ = nn_model.kneighbors(means.numpy())
         avg_dist = torch.from_numpy(distances[:, 1:]).float().mean(dim=-1, keepdim=True)
+    elif scale_init == "knn_hip":
+        from .density import knn
+
+        pts = means.to(device)
+        _, d2 = knn(pts, pts, 3, skip=1, return_d2=True)                        # skip = 1: the point itself
+        avg_dist = d2.sqrt().mean(dim=-1, keepdim=True).cpu()
     elif scale_init == "closed_form":
         avg_dist = torch.full((N, 1), mean_3nn_distance_closed_form(N))
     else:

@@ -57,7 +57,8 @@ extern "C" {
  * Pearson depth losses; dnsplat_ags_normal_loss / dnsplat_ags_normal_scratch_bytes: the filtered normal loss of the AGS-Mesh strategy;
  * dnsplat_depth_edge_valid / dnsplat_sample_valid_pixels / dnsplat_backproject_points / dnsplat_backproject_args /
  * dnsplat_pointcloud_scratch_bytes: the oriented point cloud of the mesh exporter; dnsplat_eval_metrics / dnsplat_eval_metrics_args /
- * dnsplat_eval_metrics_scratch_bytes: the evaluation scores). */
+ * dnsplat_eval_metrics_scratch_bytes: the evaluation scores; dnsplat_knn_grid_dim / dnsplat_knn_index_bytes / dnsplat_knn_build /
+ * dnsplat_knn_query / dnsplat_density_pack / dnsplat_density_eval / dnsplat_density_args: the Gaussian density field). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -683,6 +684,58 @@ typedef struct dnsplat_eval_metrics_args {
 } dnsplat_eval_metrics_args;
 size_t dnsplat_eval_metrics_scratch_bytes(int32_t width, int32_t height);   /* 0 for an invalid size */
 int dnsplat_eval_metrics(const dnsplat_eval_metrics_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ Gaussian density field (added after ABI 15, found by symbol)
+ * The reference's get_closest_gaussians / get_density / get_density_grad (dn_model.py:1061-1135, :1449-1494; utils/knn.py:29-43) for the
+ * marching-cubes exporter, the density_grad branch of the point-cloud exporter and the 3-NN scale initialisation.  Everything is
+ * caller-allocated and nothing is read on the host.
+ *
+ * dnsplat_knn_build — a spatial index over N means [N,3]: a uniform grid of dnsplat_knn_grid_dim(N) cells per axis (a host function of N
+ *   alone, about two points per cell, at most DNSPLAT_KNN_MAX_GRID) over their bounding box, which stays in a 64-byte header on the
+ *   device.  `index` holds dnsplat_knn_index_bytes(N) bytes, 16-byte aligned; the part behind the sorted copy is scratch of the build.
+ *   An axis without extent gets one layer of cells.  In-cell order is ascending Gaussian index: equal inputs give equal bytes.
+ *   Two memsets and six launches.
+ * dnsplat_knn_query — for each of M queries [M,3] the neighbours of rank skip .. skip + k - 1 under the key (d2, index) ascending,
+ *   d2 = fma(dz, dz, fma(dy, dy, dx dx)) in DOUBLE with dx = (double)q.x - (double)p.x: sklearn's fp64 ranking, index-exact.  skip = 1 is
+ *   knn_sk's dropped first column.  out_idx int32 [M,k]; out_d2 fp32 [M,k] or NULL.  A query with a non-finite coordinate gets a row of
+ *   -1 (d2 nan) and reads nothing.  k + skip <= DNSPLAT_KNN_MAX_K, else DNSPLAT_ERR_UNSUPPORTED; k + skip > N, k < 1, skip < 0:
+ *   DNSPLAT_ERR_INVALID_ARG.  One launch.
+ * dnsplat_density_pack — records [N,16]: mean, sigmoid(opacity), M = R(q / max(|q|, 1e-12)) diag(1 / max(exp(s), 1e-3)) row-major, 3 pad
+ *   (scale_rot_to_inv_cov3d(..., return_sqrt=True), dn_model.py:1603-1611).
+ * dnsplat_density_eval — per sample x, over its neighbours j in rank order:  v = M_j^T (x - mu_j),  m2 = clamp(|v|^2, 0, 1e8),
+ *     density = sum_j o_j exp(-m2 / 2);  if density >= 1: density / (density + 1e-5);  max(density, 1e-4)
+ *     normal  = -g / max(|g|, 1e-12),  g = sum over the first num_closest neighbours of m2 M_j v
+ *   Samples: `samples` [M,3], or with samples == NULL the lattice X[Rx] x Y[Ry] x Z[Rz], row (ix Ry + iy) Rz + iz (meshgrid `ij`).
+ *   mask (bytes, one per sample) == 0: density = fill, normal = 0, nothing evaluated.  Neighbours: `neighbors` [M,k] int32 or int64
+ *   (any index outside [0, N) makes the row nan), or with neighbors == NULL the search of dnsplat_knn_query run in the same thread
+ *   (index, k, skip) — no [M,k] tensor exists; both give equal bits.  density and normals are optional, not both NULL.  One launch. */
+#define DNSPLAT_KNN_MAX_K 32
+#define DNSPLAT_KNN_MAX_GRID 128
+typedef struct dnsplat_density_args {
+    int32_t N;
+    const void *index;          /* dnsplat_knn_build's; may be NULL with neighbors */
+    const float *records;       /* [N,16] of dnsplat_density_pack */
+    int64_t M;                  /* rows of samples; ignored for a lattice */
+    const float *samples;       /* [M,3] or NULL */
+    const float *X, *Y, *Z;     /* device [Rx], [Ry], [Rz]; looked at without samples */
+    int32_t Rx, Ry, Rz;
+    const uint8_t *mask;        /* one byte per sample or NULL */
+    float fill;
+    const void *neighbors;      /* [M,k] or NULL */
+    int32_t neighbors_int64;    /* 0: int32, 1: int64 */
+    int32_t k, skip;            /* skip is ignored with neighbors */
+    int32_t num_closest;        /* neighbours that enter the normal, 0 = k */
+    float *density;             /* [M] or NULL */
+    float *normals;             /* [M,3] or NULL */
+} dnsplat_density_args;
+int32_t dnsplat_knn_grid_dim(int32_t N);      /* 0 for N < 1 */
+size_t dnsplat_knn_index_bytes(int32_t N);    /* 0 for N < 1 */
+int dnsplat_knn_build(int32_t N, const float *means, void *index, dnsplat_stream_t stream);
+int dnsplat_knn_query(int32_t N, const void *index, int64_t M, const float *queries, int32_t k, int32_t skip, int32_t *out_idx,
+                      float *out_d2, dnsplat_stream_t stream);
+int dnsplat_density_pack(int32_t N, const float *means, const float *scales_log, const float *quats, const float *opacities_logit,
+                         float *records, dnsplat_stream_t stream);
+int dnsplat_density_eval(const dnsplat_density_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
