@@ -28,6 +28,8 @@ from . import export  # noqa: F401
 from .export import OrientedPointCloud, export_oriented_points  # noqa: F401
 from . import density, torch_density  # noqa: F401
 from .density import GaussianDensityField, build_index, density_volume, install_density, knn  # noqa: F401
+from . import levelset, torch_levelset  # noqa: F401
+from .levelset import LevelSetCloud, export_level_set_points, install_level_sets, level_surface_points  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -36,5 +38,6 @@ __all__ = [
     "fused_metrics", "torch_metrics", "PearsonDepthLoss", "LocalPearsonDepthLoss", "pearson_depth",
     "local_pearson_depth", "ags_normal_loss", "ags_mesh_loss_fused", "export", "OrientedPointCloud",
     "export_oriented_points", "density", "torch_density", "GaussianDensityField", "build_index", "density_volume", "install_density", "knn",
+    "levelset", "torch_levelset", "LevelSetCloud", "export_level_set_points", "install_level_sets", "level_surface_points",
     "build_library", "load_library", "DnsplatError",
 ]

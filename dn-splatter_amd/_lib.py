@@ -172,6 +172,27 @@ class DensityArgs(ctypes.Structure):
     ]
 
 
+class LevelRaysArgs(ctypes.Structure):
+    _fields_ = [
+        ("width", c_int32), ("height", c_int32), ("depth", c_void_p), ("mask", c_void_p),
+        ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("xform", c_void_p), ("range", c_void_p),
+        ("N", c_int32), ("index", c_void_p), ("records", c_void_p), ("scales_log", c_void_p), ("quats", c_void_p),
+        ("neighbors", c_void_p), ("neighbors_int64", c_int32), ("n_levels", c_int32), ("levels", c_float * 8), ("lane_map", c_int32),
+        ("t_hit", c_void_p), ("valid", c_void_p), ("closest", c_void_p), ("first_above", c_void_p), ("densities", c_void_p),
+    ]
+
+
+class LevelPointsArgs(ctypes.Structure):
+    _fields_ = [
+        ("width", c_int32), ("height", c_int32), ("depth", c_void_p), ("rgb", c_void_p), ("mask", c_void_p),
+        ("indices", c_void_p), ("counts", c_void_p), ("n_rows", c_int32),
+        ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("xform", c_void_p), ("crop", c_void_p),
+        ("t_hit", c_void_p), ("closest", c_void_p), ("normal_mode", c_int32), ("gauss_normals", c_void_p),
+        ("N", c_int32), ("index", c_void_p), ("records", c_void_p),
+        ("points", c_void_p), ("colors", c_void_p), ("normals", c_void_p), ("capacity", c_int64), ("state", c_void_p), ("scratch", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -196,6 +217,8 @@ EXPORTS = [
     # likewise: the Gaussian density field (exact k-NN, density, normals, volume)
     "dnsplat_knn_grid_dim", "dnsplat_knn_index_bytes", "dnsplat_knn_build", "dnsplat_knn_query", "dnsplat_density_pack",
     "dnsplat_density_eval",
+    # likewise: the level-set surface points (the SuGaR ray search)
+    "dnsplat_level_rays", "dnsplat_level_points",
 ]
 
 _lib = None
@@ -293,6 +316,8 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_knn_query.argtypes = [c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
         L.dnsplat_density_pack.argtypes = [c_int32] + [c_void_p] * 6
         L.dnsplat_density_eval.argtypes = [ctypes.POINTER(DensityArgs), c_void_p]
+        L.dnsplat_level_rays.argtypes = [ctypes.POINTER(LevelRaysArgs), c_void_p]
+        L.dnsplat_level_points.argtypes = [ctypes.POINTER(LevelPointsArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",

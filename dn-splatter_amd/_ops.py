@@ -12,7 +12,7 @@ dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rast
 get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
 
 One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
-``enqueue``, ``_backproject_args``, ``_eval_metrics_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
+``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, DensityArgs, EvalMetricsArgs, DnPost, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -377,6 +377,42 @@ def _density_args(N, index, records, samples, lattice, mask, fill, neighbors, k,
     a.neighbors_int64 = int(neighbors is not None and neighbors.dtype == torch.int64)
     a.k, a.skip, a.num_closest = k, skip, num_closest
     a.density, a.normals = _ptr(density), _ptr(normals)
+    return a
+
+
+def _level_rays_args(width, height, depth, mask, intrinsics, xform, range_table, N, index, records, scales_log, quats, neighbors, levels,
+                     lane_map, t_hit, valid, closest, first_above, densities):
+    a = LevelRaysArgs()
+    a.width, a.height = width, height
+    a.depth, a.mask = _ptr(depth), _ptr(mask)
+    a.fx, a.fy, a.cx, a.cy = intrinsics
+    a.xform, a.range = _ptr(xform), _ptr(range_table)
+    a.N, a.index, a.records, a.scales_log, a.quats = N, _ptr(index), _ptr(records), _ptr(scales_log), _ptr(quats)
+    a.neighbors = _ptr(neighbors)
+    a.neighbors_int64 = int(neighbors is not None and neighbors.dtype == torch.int64)
+    a.n_levels = len(levels)
+    for l, v in enumerate(levels[:8]):
+        a.levels[l] = v
+    a.lane_map = lane_map
+    a.t_hit, a.valid, a.closest = _ptr(t_hit), _ptr(valid), _ptr(closest)
+    a.first_above, a.densities = _ptr(first_above), _ptr(densities)
+    return a
+
+
+def _level_points_args(width, height, depth, rgb, mask, indices, counts, intrinsics, xform, crop, t_hit, closest, normal_mode,
+                       gauss_normals, N, index, records, points, colors, normals, state, scratch):
+    a = LevelPointsArgs()
+    a.width, a.height = width, height
+    a.depth, a.rgb, a.mask = _ptr(depth), _ptr(rgb), _ptr(mask)
+    a.indices, a.counts, a.n_rows = _ptr(indices), _ptr(counts), indices.numel()
+    a.fx, a.fy, a.cx, a.cy = intrinsics
+    a.xform, a.crop = _ptr(xform), _ptr(crop)
+    a.t_hit, a.closest = _ptr(t_hit), _ptr(closest)
+    a.normal_mode, a.gauss_normals = normal_mode, _ptr(gauss_normals)
+    a.N, a.index, a.records = N, _ptr(index), _ptr(records)
+    a.points, a.colors, a.normals = _ptr(points), _ptr(colors), _ptr(normals)
+    a.capacity = points.shape[0]
+    a.state, a.scratch = _ptr(state), _ptr(scratch)
     return a
 
 

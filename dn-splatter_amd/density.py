@@ -100,6 +100,9 @@ class GaussianDensityField:
             raise ValueError(f"for {N} means: scales [N,3], quats [N,4], opacities [N,1]; got {tuple(scales.shape)}, {tuple(quats.shape)}, "
                              f"{tuple(opacities.shape)}")
         self.N = N
+        # the level-set ray step reads them per closest Gaussian.  Copies, as the records are: the field is a snapshot, and an optimiser
+        # step on the model's parameters must not leave the ray step with other scales than the records were packed from
+        self.scales_log, self.quats = scales.clone(), quats.clone()
         self.index = KnnIndex(means)
         self.records = torch.empty(N, RECORD_FLOATS, dtype=torch.float32, device=means.device)
         L = _lib.lib()

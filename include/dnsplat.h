@@ -58,7 +58,8 @@ extern "C" {
  * dnsplat_depth_edge_valid / dnsplat_sample_valid_pixels / dnsplat_backproject_points / dnsplat_backproject_args /
  * dnsplat_pointcloud_scratch_bytes: the oriented point cloud of the mesh exporter; dnsplat_eval_metrics / dnsplat_eval_metrics_args /
  * dnsplat_eval_metrics_scratch_bytes: the evaluation scores; dnsplat_knn_grid_dim / dnsplat_knn_index_bytes / dnsplat_knn_build /
- * dnsplat_knn_query / dnsplat_density_pack / dnsplat_density_eval / dnsplat_density_args: the Gaussian density field). */
+ * dnsplat_knn_query / dnsplat_density_pack / dnsplat_density_eval / dnsplat_density_args: the Gaussian density field;
+ * dnsplat_level_rays / dnsplat_level_points / dnsplat_level_rays_args / dnsplat_level_points_args: the level-set surface points). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -736,6 +737,100 @@ int dnsplat_knn_query(int32_t N, const void *index, int64_t M, const float *quer
 int dnsplat_density_pack(int32_t N, const float *means, const float *scales_log, const float *quats, const float *opacities_logit,
                          float *records, dnsplat_stream_t stream);
 int dnsplat_density_eval(const dnsplat_density_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ level-set surface points (added after ABI 15, found by symbol)
+ * The per-camera hot path of the reference's LevelSetExtractor (export_mesh.py:514-697), DNSplatterModel.compute_level_surface_points
+ * (dn_model.py:1229-1447: the SuGaR ray search), one thread per pixel.  Everything is caller-allocated; nothing is read on the host,
+ * allocated or synchronised; no atomic: equal inputs give equal bits.  Per pixel i = v W + u, in raster order:
+ *   depth      d = mask && !mask[i] ? 0 : depth[i].  A pixel with d <= 0 takes no part.  A pixel with a non-finite d (or a non-finite
+ *              point) takes no part either and reads nothing — OUR CHOICE: the reference would raise inside sklearn.
+ *   point      p = the world point of dnsplat_backproject_points, same order of operations, bit-equal; o = t of xform (c2w[:3, 3]);
+ *              dir = (p - o) / max(|p - o|, 1e-12).
+ *   neighbours knn_sk(means, p, k = 16): dnsplat_knn_query with k = 16, skip = 1 — knn_sk asks for 17 and drops the nearest, so these are
+ *              ranks 1 .. 16 (the reference's quirk, kept).  "The closest Gaussian" c is column 0 of that result, rank 1.
+ *   ray step   std = | exp(s_c) * (R(q_c / |q_c|)^T w) |, w = (o - mu_c) / |o - mu_c| (:1266-1275), computed in the thread.  std and dir
+ *              are formed in double from the fp32 inputs and rounded once.
+ *   samples    x_j = p + (r_j std) dir, j = 0 .. 20, r = the caller's DNSPLAT_LEVEL_RANGE_POINTS floats (torch.linspace(-3, 3, 21)).
+ *   densities  D_j = sum_k o_k exp(-clamp(|M_k^T (x_j - mu_k)|^2, 0, 1e8) / 2) over the 16 neighbours OF p in rank order (no search per
+ *              sample; the records of dnsplat_density_pack, the evaluation of dnsplat_density_eval); if D_j >= 1: D_j / (D_j + 1e-5).
+ *              There is NO 1e-4 floor here, unlike get_density.  x_j - mu_k is formed as (p - mu_k) + (r_j std) dir in fp32: x_j
+ *              itself, rounded to an ulp of |p|, would cost more accuracy through M_k than the whole evaluation does.  The analytical
+ *              normal forms x - mu_k the same way, (p - mu_k) + t dir.
+ *   hit test   per level L: a = the first j with D_j > L (strict).  The pixel is EMPTY unless D_0 < L (strict) and such an a >= 1 exists.
+ *   hit        t = ((L - D_{a-1}) / (D_a - D_{a-1})) (T_a - T_{a-1}) + T_{a-1},  T_j = r_j std, in that order in fp32 without contraction.
+ *              The point is p + t dir, the colour rgb[i] bit for bit.
+ *   normal     DNSPLAT_LEVEL_NORMAL_CLOSEST: row c of the model's `normals` parameter.  DNSPLAT_LEVEL_NORMAL_ANALYTICAL:
+ *              -normalize(sum_k w_k M_k (M_k^T (x - mu_k))) at the hit point x, w_k the neighbour's term of the density sum (:1388-1418;
+ *              NOT get_density_grad's weight m2).  normalize(x) = x / max(|x|, 1e-12).
+ * dnsplat_level_rays — one launch: depth .. hit for up to DNSPLAT_LEVEL_MAX_LEVELS levels.
+ *   t_hit [n_levels,P] (nan where empty), valid [n_levels,P] bytes, closest [P] int32 (-1 where the pixel took no part); optional
+ *   first_above [n_levels,P] int32 (0 where empty) and densities [P,21] (nan where the pixel took no part).
+ *   Neighbours: `neighbors` [P,16] int32 or int64 (read for the participating pixels; a row with an index outside [0, N) takes no part),
+ *   or NULL: the search runs in the thread on `index`.  Both give equal bits.
+ *   lane_map: DNSPLAT_LEVEL_MAP_BLOCK maps a wave to an 8 x 8 block of pixels (its lanes walk the same cells of the index, as the
+ *   lattice's 4 x 4 x 4 bricks do), DNSPLAT_LEVEL_MAP_ROW to 64 consecutive pixels in raster order.  The results do not depend on it.
+ * dnsplat_level_points — per level, for the rows of indices / counts as dnsplat_sample_valid_pixels leaves them for the level's validity
+ *   bytes: point, colour, normal; the crop box, the append at the device cursor state[0] and the flags state[1] (overflow), state[2]
+ *   (index outside the frame) exactly as dnsplat_backproject_points; a row whose t_hit is nan (an empty pixel) is dropped.  t_hit and
+ *   closest are the level's [P] row and the [P] tensor of dnsplat_level_rays.  The analytical normal re-runs the search for the selected
+ *   rows only.  scratch: dnsplat_pointcloud_scratch_bytes(width, height, n_rows) bytes.  Three launches.
+ * Returns without a launch: DNSPLAT_ERR_INVALID_ARG for NULL required pointers, width or height < 1, n_levels outside 1 .. 8, N < 17, an
+ * unknown lane_map or normal_mode; DNSPLAT_ERR_UNSUPPORTED for more than 2^31 - 1 pixels. */
+#define DNSPLAT_LEVEL_RANGE_POINTS 21
+#define DNSPLAT_LEVEL_MAX_LEVELS 8
+#define DNSPLAT_LEVEL_KNN 16
+#define DNSPLAT_LEVEL_MAP_BLOCK 0
+#define DNSPLAT_LEVEL_MAP_ROW 1
+#define DNSPLAT_LEVEL_NORMAL_CLOSEST 0
+#define DNSPLAT_LEVEL_NORMAL_ANALYTICAL 1
+typedef struct dnsplat_level_rays_args {
+    int32_t width, height;
+    const float *depth;         /* [H,W] */
+    const uint8_t *mask;        /* [H,W] bytes or NULL */
+    float fx, fy, cx, cy;
+    const float *xform;         /* device [21], as dnsplat_backproject_args */
+    const float *range;         /* device [DNSPLAT_LEVEL_RANGE_POINTS] */
+    int32_t N;
+    const void *index;          /* dnsplat_knn_build's; may be NULL with neighbors */
+    const float *records;       /* [N,16] of dnsplat_density_pack */
+    const float *scales_log;    /* [N,3] */
+    const float *quats;         /* [N,4] wxyz, any norm */
+    const void *neighbors;      /* [P,16] or NULL */
+    int32_t neighbors_int64;    /* 0: int32, 1: int64 */
+    int32_t n_levels;
+    float levels[DNSPLAT_LEVEL_MAX_LEVELS];
+    int32_t lane_map;           /* DNSPLAT_LEVEL_MAP_* */
+    float *t_hit;               /* [n_levels,P] */
+    uint8_t *valid;             /* [n_levels,P] */
+    int32_t *closest;           /* [P] */
+    int32_t *first_above;       /* [n_levels,P] or NULL */
+    float *densities;           /* [P,21] or NULL */
+} dnsplat_level_rays_args;
+typedef struct dnsplat_level_points_args {
+    int32_t width, height;
+    const float *depth;         /* [H,W] */
+    const float *rgb;           /* [H,W,3] */
+    const uint8_t *mask;        /* [H,W] bytes or NULL */
+    const int32_t *indices;     /* [n_rows] flat pixel indices */
+    const int32_t *counts;      /* device {n, m} of dnsplat_sample_valid_pixels or NULL */
+    int32_t n_rows;
+    float fx, fy, cx, cy;
+    const float *xform;         /* device [21] */
+    const float *crop;          /* device [15] or NULL */
+    const float *t_hit;         /* [P]: the level's row */
+    const int32_t *closest;     /* [P] */
+    int32_t normal_mode;        /* DNSPLAT_LEVEL_NORMAL_* */
+    const float *gauss_normals; /* [N,3], the model's `normals`; CLOSEST only */
+    int32_t N;
+    const void *index;          /* ANALYTICAL only */
+    const float *records;       /* ANALYTICAL only */
+    float *points, *colors, *normals;   /* [capacity,3] */
+    int64_t capacity;
+    int64_t *state;             /* device int64 [3]: cursor, overflow, index out of range */
+    void *scratch;
+} dnsplat_level_points_args;
+int dnsplat_level_rays(const dnsplat_level_rays_args *args, dnsplat_stream_t stream);
+int dnsplat_level_points(const dnsplat_level_points_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
