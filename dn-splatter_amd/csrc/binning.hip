@@ -6,8 +6,9 @@
 //
 // Same result, different route.  The reference sorts I = n_isects 12-byte pairs on ~45 key bits
 // (6 radix passes over I).  Here:
-//   1. the N Gaussians are stably radix-sorted once by their 32 depth bits (4 passes over N, N << I); the first pass
-//      drops the culled ones (they emit nothing), the other three and the scans run over the visible Gaussians only;
+//   1. the N Gaussians are stably sorted once by their 32 depth bits (N << I), the culled ones dropped on the way (they emit
+//      nothing): below 4 M entries by ONE range partition on (key - kmin) >> shift into ~N / 1024 buckets and a stable sort of
+//      every bucket inside LDS (five launches; depth_buckets.h), from there on by four LSD radix passes (twelve);
 //   2. the (tile, gaussian) pairs of that depth order are never written out as such: the FIRST pass of the tile
 //      sort generates them on the fly — once to count its digits, once to place them (each workgroup owns 4096
 //      consecutive pairs of the emission order and finds the Gaussians they belong to through a 16-byte record
@@ -25,8 +26,11 @@
 // device word, so the whole stage can be enqueued without a host round-trip on n_isects (the
 // caller bounds it with `isect_capacity`).
 
+#include <assert.h>
+#include <string.h>
 #include "splat_common.h"
 #include "bin_ranges.h"
+#include "depth_buckets.h"
 
 namespace {
 
@@ -617,6 +621,423 @@ __global__ __launch_bounds__(TH) DNS_TI_OCCUPANCY(TH, K) void radix_scatter_kern
 }
 
 // ------------------------------------------------------------------------------------------------
+// 1. the depth sort: ONE range partition into B buckets (depth_buckets.h) + a stable sort of every bucket inside LDS.
+// Five launches — bounds, histogram, digit scan (radix_scan_kernel), scatter, bucket sorts — instead of the twelve of four LSD passes.
+// No samples, no splitters, no data-dependent launch: balance of the buckets only decides speed, a bucket of any size is sorted by
+// its own workgroup (beyond DP_CAP keys: in global memory).
+constexpr int DP_THREADS = 256;
+constexpr int DP_ITEMS = 16;                     // partition chunk = 4096 entries
+constexpr int DP_CHUNK = DP_THREADS * DP_ITEMS;
+constexpr int DP_NW = DP_THREADS / DNS_WAVE;
+constexpr int DP_CAP = DNS_DP_CAP;
+constexpr int DP_BOUNDS_WGS = 1024;              // at most that many (min, max) partials
+static_assert(DP_BOUNDS_WGS % DP_THREADS == 0, "the partials are reduced in rounds of one per thread");
+#ifndef DNS_DP_BBITS
+#define DNS_DP_BBITS 0                           // 0: by N (dns_depth_bucket_bits); 9..12 pins log2(B) for paired measurements
+#endif
+inline int dp_bbits(int N) { return DNS_DP_BBITS ? DNS_DP_BBITS : dns_depth_bucket_bits(N); }
+// consecutive chunks one workgroup of the partition takes (one column of the count table): B / 1024, so that the table of
+// B x workgroups counters — what the three kernels move besides the keys — stays about N / 4 words at every size (1 M: 1024 buckets x
+// 245 columns).  With one chunk per workgroup and 4096 buckets it would be one counter per entry.
+inline int dp_sub(int N) { const int s = (1 << dp_bbits(N)) >> 10; return s < 1 ? 1 : s; }
+inline int dp_bounds_wgs(int N)
+{
+    const int g = (N + DP_CHUNK - 1) / DP_CHUNK;
+    return g < 1 ? 1 : (g > DP_BOUNDS_WGS ? DP_BOUNDS_WGS : g);
+}
+
+// workgroup-wide (min, max) of unsigned words; every thread gets both
+__device__ __forceinline__ void dp_block_minmax(uint32_t &mn, uint32_t &mx, uint32_t *red /*[2 * DP_NW]*/)
+{
+#pragma unroll
+    for (int off = DNS_WAVE / 2; off > 0; off >>= 1) {
+        mn = min(mn, (uint32_t)__shfl_xor((int)mn, off, DNS_WAVE));
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, DNS_WAVE));
+    }
+    const int w = threadIdx.x / DNS_WAVE;
+    if (lane_id() == 0) { red[2 * w] = mn; red[2 * w + 1] = mx; }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < DP_NW; ++i) { mn = min(mn, red[2 * i]); mx = max(mx, red[2 * i + 1]); }
+    __syncthreads();
+}
+
+// smallest and largest depth key of the visible Gaussians, one (min, max) partial per workgroup: (0xFFFFFFFF, 0) where it saw none
+__global__ __launch_bounds__(DP_THREADS) void depth_bounds_kernel(const int32_t *__restrict__ radii, const float *__restrict__ depths,
+                                                                  uint32_t n, uint32_t *__restrict__ part)
+{
+    __shared__ uint32_t red[2 * DP_NW];
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+    constexpr int U = 4;
+    for (uint32_t i0 = blockIdx.x * (DP_THREADS * U) + threadIdx.x; i0 < n; i0 += gridDim.x * (DP_THREADS * U)) {
+        int32_t r[U];
+        uint32_t k[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t i = min(i0 + u * DP_THREADS, n - 1u);
+            r[u] = radii[i];
+            k[u] = __float_as_uint(depths[i]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (r[u] > 0) { mn = min(mn, k[u]); mx = max(mx, k[u]); }
+    }
+    dp_block_minmax(mn, mx, red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = mn; part[2 * blockIdx.x + 1] = mx; }
+}
+
+// Bucket counts of the partition per workgroup (`sub` consecutive chunks), table[d][workgroup] as in radix_hist_kernel.  Every workgroup folds the (min, max) partials
+// itself; the first leaves kmin and the shift in ks[0..1] for the two kernels behind it.  Culled Gaussians are not counted.
+template <int BBITS>
+__global__ __launch_bounds__(DP_THREADS) void depth_part_hist_kernel(const int32_t *__restrict__ radii, const float *__restrict__ depths,
+                                                                     uint32_t n, const uint32_t *__restrict__ part, int n_part,
+                                                                     uint32_t *__restrict__ ks, uint32_t *__restrict__ table, int nb,
+                                                                     int sub)
+{
+    constexpr int NB = 1 << BBITS;
+    __shared__ uint32_t hist[NB];
+    __shared__ uint32_t red[2 * DP_NW];
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+    for (int i = threadIdx.x; i < n_part; i += DP_THREADS) { mn = min(mn, part[2 * i]); mx = max(mx, part[2 * i + 1]); }
+    for (int d = threadIdx.x; d < NB; d += DP_THREADS) hist[d] = 0u;
+    dp_block_minmax(mn, mx, red);                   // its barriers also publish the zeroed counters
+    uint32_t kmin = 0u;
+    int shift = 0;
+    if (mn <= mx) { kmin = mn; shift = dns_depth_bucket_shift(mn, mx, BBITS); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ks[0] = kmin; ks[1] = (uint32_t)shift; }
+    for (int c = 0; c < sub; ++c) {
+        const uint32_t base = (blockIdx.x * sub + c) * DP_CHUNK;
+        if (base >= n) break;
+        int32_t r[DP_ITEMS];
+        uint32_t k[DP_ITEMS];
+#pragma unroll
+        for (int i = 0; i < DP_ITEMS; ++i) {
+            const uint32_t idc = min(base + i * DP_THREADS + threadIdx.x, n - 1u);
+            r[i] = radii[idc];
+            k[i] = __float_as_uint(depths[idc]);
+        }
+#pragma unroll
+        for (int i = 0; i < DP_ITEMS; ++i)
+            if (base + i * DP_THREADS + threadIdx.x < n && r[i] > 0) atomicAdd(&hist[dns_depth_bucket(k[i], kmin, shift) & (NB - 1)], 1u);
+    }
+    __syncthreads();
+    for (int d = threadIdx.x; d < NB; d += DP_THREADS) table[(size_t)d * nb + blockIdx.x] = hist[d];
+}
+
+// Stable scatter of the partition: (key, entry) pairs of the visible Gaussians to their bucket's run, chunk order then position
+// within a bucket.  Ranking as in radix_scatter_kernel (match-by-digit ballots, per-wave counters); the pairs go straight from the
+// registers to their place — with about as many buckets as a chunk has keys there are no runs an LDS staging could coalesce.
+// Leaves n_ranked (count_out) and, by the first workgroup, the B + 1 bucket starts.
+template <int BBITS>
+__global__ __launch_bounds__(DP_THREADS) void depth_part_scatter_kernel(
+    const int32_t *__restrict__ radii, const float *__restrict__ depths, uint32_t n, const uint32_t *__restrict__ ks,
+    uint2 *__restrict__ pairs_out, const uint32_t *__restrict__ table, const uint32_t *__restrict__ totals, int nb, int segs, int seg_len,
+    uint32_t *__restrict__ count_out, uint32_t *__restrict__ bucket_start, int sub)
+{
+    constexpr int NB = 1 << BBITS;
+    constexpr int DPT = NB / DP_THREADS;             // buckets per thread in the scans: thread t owns [t x DPT, (t + 1) x DPT)
+    static_assert(NB % DP_THREADS == 0 && DP_CHUNK <= 0xFFFF, "bucket scan layout / 16-bit chunk-local counts");
+    __shared__ __align__(4) uint16_t wave_cnt[DP_NW][NB];       // keys of (wave, bucket) so far; then the chunk-local start of that wave's keys
+    __shared__ uint32_t gbase[NB];                   // global start of the current chunk's keys of a bucket
+    __shared__ uint32_t lds_wave[DP_NW];
+    const uint32_t base0 = blockIdx.x * sub * DP_CHUNK;
+    if (base0 >= n) return;
+    const uint32_t kmin = ks[0];
+    const int shift = (int)ks[1];
+    const int w = threadIdx.x / DNS_WAVE;
+    const uint32_t lane = lane_id();
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    {
+        // global start of this workgroup's keys of a bucket = (keys in smaller buckets) + (same bucket, earlier workgroups): the
+        // bucket totals are the sums of the scan's segments, the table entry is relative to the workgroup's segment
+        uint32_t pre_tot[DPT], pre_tab[DPT];
+        const int my_seg = (int)blockIdx.x / seg_len;
+        uint32_t tsum = 0u;
+#pragma unroll
+        for (int q = 0; q < DPT; ++q) {
+            const int d = threadIdx.x * DPT + q;
+            pre_tab[q] = table[(size_t)d * nb + blockIdx.x];
+            pre_tot[q] = 0u;
+            for (int sg = 0; sg < segs; ++sg) {
+                const uint32_t v = totals[d * segs + sg];
+                pre_tot[q] += v;
+                if (sg < my_seg) pre_tab[q] += v;
+            }
+            tsum += pre_tot[q];
+        }
+        uint32_t total;
+        const uint32_t inc = block_incl_scan<DP_NW>(tsum, lds_wave, total);
+        uint32_t run = inc - tsum;                     // keys in the buckets before this thread's
+#pragma unroll
+        for (int q = 0; q < DPT; ++q) {
+            const int d = threadIdx.x * DPT + q;
+            gbase[d] = run + pre_tab[q];
+            if (blockIdx.x == 0) bucket_start[d] = run;
+            run += pre_tot[q];
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) { bucket_start[NB] = total; *count_out = total; }
+    }
+    for (int c = 0; c < sub; ++c) {
+        const uint32_t base = base0 + c * DP_CHUNK;
+        if (base >= n) break;
+        {
+            uint32_t *z = reinterpret_cast<uint32_t *>(&wave_cnt[0][0]);
+            for (int i = threadIdx.x; i < DP_NW * NB / 2; i += DP_THREADS) z[i] = 0u;
+        }
+        __syncthreads();
+        const uint32_t wave_start = base + w * (DNS_WAVE * DP_ITEMS);
+        uint32_t key[DP_ITEMS];
+        int32_t rad[DP_ITEMS];
+        uint16_t rnk[DP_ITEMS];
+#pragma unroll
+        for (int r = 0; r < DP_ITEMS; ++r) {
+            const uint32_t idc = min(wave_start + r * DNS_WAVE + lane, n - 1u);
+            rad[r] = radii[idc];
+            key[r] = __float_as_uint(depths[idc]);
+        }
+        uint32_t live = 0u;
+#pragma unroll
+        for (int r = 0; r < DP_ITEMS; ++r) {
+            const uint32_t idx = wave_start + r * DNS_WAVE + lane;
+            const bool valid = idx < n && rad[r] > 0;
+            live |= (valid ? 1u : 0u) << r;
+            const uint32_t d = valid ? (dns_depth_bucket(key[r], kmin, shift) & (NB - 1)) : 0u;
+            uint64_t m = dns_ballot(valid);
+#pragma unroll
+            for (int bit = 0; bit < BBITS; ++bit) {
+                const bool b = (d >> bit) & 1;
+                const uint64_t bal = dns_ballot(b);
+                m &= b ? bal : ~bal;
+            }
+            const uint32_t prior = wave_cnt[w][d];
+            const uint32_t below = __popcll(m & lt_mask);
+            rnk[r] = (uint16_t)(prior + below);
+            if (valid && below == 0) wave_cnt[w][d] = (uint16_t)(prior + __popcll(m));
+        }
+        __syncthreads();
+        uint32_t cnt[DPT];                             // this chunk's keys of the thread's buckets
+#pragma unroll
+        for (int q = 0; q < DPT; ++q) {
+            const int d = threadIdx.x * DPT + q;
+            uint32_t run = 0u;
+#pragma unroll
+            for (int i = 0; i < DP_NW; ++i) {
+                const uint32_t v = wave_cnt[i][d];
+                wave_cnt[i][d] = (uint16_t)run;
+                run += v;
+            }
+            cnt[q] = run;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < DP_ITEMS; ++r)
+            if ((live >> r) & 1u) {
+                const uint32_t d = dns_depth_bucket(key[r], kmin, shift) & (NB - 1);
+                const uint32_t dst = gbase[d] + wave_cnt[w][d] + rnk[r];
+                pairs_out[dst] = make_uint2(key[r], wave_start + r * DNS_WAVE + lane);
+            }
+        __syncthreads();
+        // the next chunk's keys of a bucket go behind this one's (its stores are two barriers away)
+#pragma unroll
+        for (int q = 0; q < DPT; ++q) gbase[threadIdx.x * DPT + q] += cnt[q];
+    }
+}
+
+// One stable LSD pass of a workgroup over n (key, entry) pairs in global memory, src -> dst, on `dbits` <= 8 bits of key - kmin at
+// `sh` — the route of a bucket that does not fit into LDS: slow, rare, and correct for any n.  Counts in the workgroup's own LDS counters, barriers only.  Per round of DP_THREADS pairs: rank within
+// the wave by ballots, the waves before through wave_cnt, the rounds before through dig_run.
+__device__ __forceinline__ void dp_lsd_pass(const uint2 *src, uint2 *dst, uint32_t n, uint32_t kmin, int sh, int dbits,
+                                            uint32_t *dig_run /*[256]*/, uint32_t (*wave_cnt)[256] /*[DP_NW]*/, uint32_t *lds_wave)
+{
+    static_assert(DP_THREADS == 256, "one thread per digit");
+    const uint32_t mask = (1u << dbits) - 1u;
+    const int w = threadIdx.x / DNS_WAVE;
+    const uint32_t lane = lane_id();
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    dig_run[threadIdx.x] = 0u;
+#pragma unroll
+    for (int i = 0; i < DP_NW; ++i) wave_cnt[i][threadIdx.x] = 0u;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += DP_THREADS) atomicAdd(&dig_run[((src[i].x - kmin) >> sh) & mask], 1u);
+    __syncthreads();
+    {
+        const uint32_t v = dig_run[threadIdx.x];
+        uint32_t tot;
+        const uint32_t inc = block_incl_scan<DP_NW>(v, lds_wave, tot);
+        dig_run[threadIdx.x] = inc - v;
+    }
+    __syncthreads();
+    for (uint32_t b0 = 0; b0 < n; b0 += DP_THREADS) {
+        const uint32_t i = b0 + threadIdx.x;
+        const bool valid = i < n;
+        const uint2 p = src[valid ? i : n - 1u];
+        const uint32_t d = valid ? (((p.x - kmin) >> sh) & mask) : 0u;
+        uint64_t m = dns_ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const bool b = (d >> bit) & 1;
+            const uint64_t bal = dns_ballot(b);
+            m &= b ? bal : ~bal;
+        }
+        const uint32_t below = __popcll(m & lt_mask);
+        if (valid && below == 0) wave_cnt[w][d] = __popcll(m);
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = dig_run[d] + below;
+#pragma unroll
+            for (int q = 0; q < DP_NW; ++q)
+                if (q < w) pos += wave_cnt[q][d];
+            dst[pos] = p;
+        }
+        __syncthreads();
+        {
+            uint32_t s = 0u;
+#pragma unroll
+            for (int q = 0; q < DP_NW; ++q) { s += wave_cnt[q][threadIdx.x]; wave_cnt[q][threadIdx.x] = 0u; }
+            dig_run[threadIdx.x] += s;
+        }
+        __syncthreads();
+    }
+}
+
+// the sorted bucket to its place: entry ids to vals_out and, in the same store, the tile box and tile count of every entry in depth
+// order (what radix_scatter_kernel<.., BOXG> leaves behind on the four-pass route).  Four random box gathers of a thread are in flight
+// together (one by one, each round of the loop was a gather's latency).
+__device__ __forceinline__ void dp_store_bucket(const uint2 *res, uint32_t s, uint32_t n, uint32_t *__restrict__ vals_out,
+                                                const int2 *__restrict__ box_in, int2 *__restrict__ box_out,
+                                                uint32_t *__restrict__ tiles_out)
+{
+    constexpr int U = 4;
+    for (uint32_t i0 = threadIdx.x; i0 < n; i0 += U * DP_THREADS) {
+        uint32_t v[U];
+        int2 bx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = res[min(i0 + u * DP_THREADS, n - 1u)].y;
+        if (box_in) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) bx[u] = box_in[v[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t i = i0 + u * DP_THREADS;
+            if (i < n) {
+                vals_out[s + i] = v[u];
+                if (box_in) {
+                    box_out[s + i] = bx[u];
+                    tiles_out[s + i] = ((uint32_t)bx[u].y & 0xffffu) * ((uint32_t)bx[u].y >> 16);
+                }
+            }
+        }
+    }
+}
+
+// A bucket of n <= DP_CAP pairs sorted inside LDS, every pair held in a register between the passes: wave w owns the pairs
+// [w x 64 x ipw, (w + 1) x 64 x ipw) of the current order, ipw = ceil(n / DP_THREADS) per lane.  Per pass ONE ranking chain (as in the
+// partition's scatter), one prefix over waves and digits, one scatter into `buf` — four barriers, whatever n — and no second buffer:
+// nothing reads `buf` between the reload behind one scatter and the next scatter.  Leaves the sorted pairs in buf[0..n).
+__device__ __forceinline__ void dp_sort_in_lds(const uint2 *__restrict__ in, uint32_t n, uint32_t kmin, int passes, int dbits, uint2 *buf,
+                                               uint32_t *dig_start /*[256]*/, uint32_t (*wave_cnt)[256] /*[DP_NW]*/, uint32_t *lds_wave)
+{
+    constexpr int ITEMS = DP_CAP / DP_THREADS;
+    const int w = threadIdx.x / DNS_WAVE;
+    const uint32_t lane = lane_id();
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int ipw = (int)((n + DP_THREADS - 1) / DP_THREADS);
+    const uint32_t first = (uint32_t)w * DNS_WAVE * ipw + lane;
+    const uint32_t mask = (1u << dbits) - 1u;
+    uint2 p[ITEMS];
+    uint32_t rnk[ITEMS];
+#pragma unroll
+    for (int r = 0; r < ITEMS; ++r)
+        if (r < ipw) p[r] = in[min(first + r * DNS_WAVE, n - 1u)];
+    if (passes == 0) {
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r)
+            if (r < ipw && first + r * DNS_WAVE < n) buf[first + r * DNS_WAVE] = p[r];
+    }
+    for (int pass = 0; pass < passes; ++pass) {
+        const int sh = pass * dbits;
+#pragma unroll
+        for (int i = 0; i < DP_NW; ++i) wave_cnt[i][threadIdx.x] = 0u;
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r)
+            if (r < ipw) {
+                const bool valid = first + r * DNS_WAVE < n;
+                const uint32_t d = valid ? (((p[r].x - kmin) >> sh) & mask) : 0u;
+                uint64_t m = dns_ballot(valid);
+#pragma unroll
+                for (int bit = 0; bit < 8; ++bit) {
+                    const bool b = (d >> bit) & 1;
+                    const uint64_t bal = dns_ballot(b);
+                    m &= b ? bal : ~bal;
+                }
+                const uint32_t prior = wave_cnt[w][d];
+                const uint32_t below = __popcll(m & lt_mask);
+                rnk[r] = prior + below;
+                if (valid && below == 0) wave_cnt[w][d] = prior + __popcll(m);
+            }
+        __syncthreads();
+        {
+            uint32_t cnt = 0u;
+#pragma unroll
+            for (int i = 0; i < DP_NW; ++i) {
+                const uint32_t c = wave_cnt[i][threadIdx.x];
+                wave_cnt[i][threadIdx.x] = cnt;
+                cnt += c;
+            }
+            uint32_t tot;
+            const uint32_t inc = block_incl_scan<DP_NW>(cnt, lds_wave, tot);
+            dig_start[threadIdx.x] = inc - cnt;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r)
+            if (r < ipw && first + r * DNS_WAVE < n) {
+                const uint32_t d = ((p[r].x - kmin) >> sh) & mask;
+                buf[dig_start[d] + wave_cnt[w][d] + rnk[r]] = p[r];
+            }
+        __syncthreads();
+        if (pass + 1 < passes) {
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r)
+                if (r < ipw) p[r] = buf[min(first + r * DNS_WAVE, n - 1u)];
+        }
+    }
+    __syncthreads();
+}
+
+// One workgroup per bucket: its keys [bucket_start[b], bucket_start[b + 1]) of pairs_a are sorted stably on the low `shift` bits of
+// key - kmin — inside LDS when they fit, else in place in global memory (pairs_a <-> pairs_b, same passes) — and stored.
+__global__ __launch_bounds__(DP_THREADS) void depth_bucket_sort_kernel(const uint32_t *__restrict__ ks,
+                                                                       const uint32_t *__restrict__ bucket_start, uint2 *pairs_a,
+                                                                       uint2 *pairs_b, uint32_t *__restrict__ vals_out,
+                                                                       const int2 *__restrict__ box_in, int2 *__restrict__ box_out,
+                                                                       uint32_t *__restrict__ tiles_out)
+{
+    __shared__ uint2 buf[DP_CAP];
+    __shared__ uint32_t dig_run[256];
+    __shared__ uint32_t wave_cnt[DP_NW][256];
+    __shared__ uint32_t lds_wave[DP_NW];
+    const uint32_t s = bucket_start[blockIdx.x], n = bucket_start[blockIdx.x + 1] - s;
+    if (n == 0) return;
+    const uint32_t kmin = ks[0];
+    const int shift = (int)ks[1];
+    const int passes = dns_depth_local_passes(shift), dbits = dns_depth_local_bits(shift);
+    if (n <= (uint32_t)DP_CAP) {
+        dp_sort_in_lds(pairs_a + s, n, kmin, passes, dbits, buf, dig_run, wave_cnt, lds_wave);
+        dp_store_bucket(buf, s, n, vals_out, box_in, box_out, tiles_out);
+    } else {
+        uint2 *src = pairs_a + s, *dst = pairs_b + s;
+        for (int p = 0; p < passes; ++p) {
+            dp_lsd_pass(src, dst, n, kmin, p * dbits, dbits, dig_run, wave_cnt, lds_wave);
+            uint2 *t = src; src = dst; dst = t;
+        }
+        dp_store_bucket(src, s, n, vals_out, box_in, box_out, tiles_out);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // 3. inclusive scan of tiles_per_gauss gathered in depth order  -> cum[n], total; n = the number of depth ranks (visible Gaussians),
 // a device word the first depth pass leaves behind
 // Also leaves the gathered counts in depth order (tiles_sorted): scan_final_kernel reads them coalesced instead of repeating the
@@ -848,10 +1269,17 @@ struct BinWs {
     uint32_t *total;                          // [1] n_isects as u32
     uint32_t *status;                         // [1] reserved status word (dnsplat_bin_status_offset): 0
     uint32_t *n_ranked;                       // [1] Gaussians the depth sort kept (radii > 0) = number of depth ranks
+    // the range partition of the depth sort: no room of its own.  Its pair buffers are the two halves of jrec, its tables lie in
+    // chunk_first / key_a (see carve) — all of them written again only after the sort
+    uint32_t *dp_part;                        // [2 x DP_BOUNDS_WGS] (min, max) partials of the depth keys
+    uint32_t *dp_ks;                          // [2] kmin, shift
+    uint32_t *dp_start;                       // [B + 1] bucket starts
+    uint32_t *dp_tab;                         // [B x nb_p]
+    uint32_t *dp_totals;                      // [B x SC_MAX_SEGS]
     uint32_t *tkey_b, *tval_b;                // [cap] pairs between the two tile passes
     uint32_t *tkey_c, *tval_c;                // [cap] only with three tile passes (> 65536 tiles)
     uint32_t *tab_i;                          // [256 * nb_i]
-    int nb_n, nb_i, nb_scan;
+    int nb_n, nb_i, nb_scan, nb_p;
     size_t bytes;
 };
 
@@ -866,6 +1294,8 @@ BinWs carve(void *ws, int N, int64_t cap)
     if (b.nb_n < 1) b.nb_n = 1;
     if (b.nb_i < 1) b.nb_i = 1;
     if (b.nb_scan < 1) b.nb_scan = 1;
+    b.nb_p = (N + DP_CHUNK * dp_sub(N) - 1) / (DP_CHUNK * dp_sub(N));
+    if (b.nb_p < 1) b.nb_p = 1;
     size_t off = 0;
     char *base = (char *)ws;
     auto take = [&](size_t elems) {
@@ -887,6 +1317,20 @@ BinWs carve(void *ws, int N, int64_t cap)
     b.total = take(1);
     b.status = take(1);
     b.n_ranked = take(1);
+    {
+        // The partition's tables take no room of their own (the workspace size and layout are those of the four-pass route): they are
+        // dead before emit_prep_kernel writes the head table, so they live in it — and the count table, where it is larger than the
+        // rest of the head table (from ~0.7 M entries on), in the key buffers only the four-pass route uses (B x nb_p <= 2 N there).
+        const size_t B = (size_t)1 << dp_bbits(N), tab = B * b.nb_p;
+        uint32_t *q = b.chunk_first;
+        b.dp_part = q; q += 2 * DP_BOUNDS_WGS;
+        b.dp_ks = q; q += 64;
+        b.dp_start = q; q += align_up(B + 1, 64);
+        b.dp_totals = q; q += B * SC_MAX_SEGS;
+        const bool in_heads = (size_t)(q - b.chunk_first) + tab <= (size_t)MAX_CHUNKS;
+        b.dp_tab = in_heads ? q : b.key_a;
+        assert((size_t)(q - b.chunk_first) <= (size_t)MAX_CHUNKS && (in_heads || tab <= (size_t)(b.val_a - b.key_a)));
+    }
     // capacity-sized part
     b.tkey_b = take(c); b.tval_b = take(c);
     b.tkey_c = take(c); b.tval_c = take(c);
@@ -1111,6 +1555,23 @@ extern "C" size_t dnsplat_bin_status_offset(int32_t N, int64_t isect_capacity)
     return (size_t)((char *)w.status - (char *)nullptr);
 }
 
+// The depth order: one range partition + bucket sorts in LDS (five launches) below 2^22 entries, the four LSD passes (twelve) from there
+// on, where that route works in 4096-key chunks.  Paired against the four passes (docs/history.md §18) dnsplat_bin_prepare takes
+// 28-44 us less from 1 M to 3.9 M entries and the step clears the run-to-run spread at C2 and C3; at 5 M it is 13 us, which the step does
+// not show.  DNSPLAT_BIN_DEPTH_SORT=radix4 / =partition (read once) pins a route at every size, for A/B runs and the parity tests.
+static bool depth_sort_by_partition(int N)
+{
+    static const int pinned = [] {
+        const char *e = getenv("DNSPLAT_BIN_DEPTH_SORT");
+        return !e ? 0 : !strcmp(e, "radix4") ? 1 : !strcmp(e, "partition") ? 2 : 0;
+    }();
+    return pinned == 2 || (pinned == 0 && N < RS_LARGE_N);
+}
+
+// Which depth sort dnsplat_bin_prepare takes for N entries in this process: 1 = range partition, 0 = four LSD passes.  A diagnostic
+// found by symbol (tests, A/B scripts); not part of include/dnsplat.h.
+extern "C" int dnsplat_bin_depth_route(int32_t N) { return depth_sort_by_partition(N) ? 1 : 0; }
+
 static int check_bin(const dnsplat_bin_args *a)
 {
     if (!a) return DNSPLAT_ERR_INVALID_ARG;
@@ -1144,25 +1605,53 @@ extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t s
         // DNSPLAT_BIN_BOX_FOLD=0: the box gather as scan_sums_kernel<true> behind the depth sort (round 4 / 5) instead of inside its last pass
         static const bool box_fold = [] { const char *e = getenv("DNSPLAT_BIN_BOX_FOLD"); return !(e && e[0] == '0'); }();
         const bool fold = sorted_boxes && box_fold;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 8 * pass;
-            const bool fold_here = fold && pass == 3;
-            // pass 0 knows its element count on the host (n_ptr = NULL), reads (radii, depths) instead of a key / value pair and drops
-            // the culled Gaussians; it leaves the number it kept in w.n_ranked, which bounds every later pass and the scans
-            if (rs_items_n(N) == RS_ITEMS_N_LARGE)
-                radix_pass<uint32_t, RS_ITEMS_N_LARGE>(stream, ka, va, kb, vb, pass == 0 ? nullptr : w.n_ranked, n_u32, shift, 8, w.tab_n, w.totals,
-                                                       w.nb_n, nullptr, pass == 0 ? a->radii : nullptr, pass == 0 ? a->depths : nullptr, nullptr, 0,
-                                                       nullptr, nullptr, nullptr, pass == 0 ? w.n_ranked : nullptr,
-                                                       fold_here ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
-            else
-                radix_pass<uint32_t, RS_ITEMS_N>(stream, ka, va, kb, vb, pass == 0 ? nullptr : w.n_ranked, n_u32, shift, 8, w.tab_n, w.totals,
-                                                 w.nb_n, nullptr, pass == 0 ? a->radii : nullptr, pass == 0 ? a->depths : nullptr, nullptr, 0,
-                                                 nullptr, nullptr, nullptr, pass == 0 ? w.n_ranked : nullptr,
-                                                 fold_here ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
-            uint32_t *t = ka; ka = kb; kb = t;
-            t = va; va = vb; vb = t;
+        const bool radix4 = !depth_sort_by_partition(N);
+        if (!radix4) {
+            uint2 *pairs_a = reinterpret_cast<uint2 *>(w.jrec), *pairs_b = pairs_a + N;
+            const int n_part = dp_bounds_wgs(N), sub = dp_sub(N);
+            int segs, seg_len;
+            scan_segments(w.nb_p, segs, seg_len);
+            hipLaunchKernelGGL(depth_bounds_kernel, dim3(n_part), dim3(DP_THREADS), 0, stream, a->radii, a->depths, n_u32, w.dp_part);
+#define DNS_DEPTH_PARTITION(B)                                                                                                            \
+    do {                                                                                                                                  \
+        hipLaunchKernelGGL(depth_part_hist_kernel<B>, dim3(w.nb_p), dim3(DP_THREADS), 0, stream, a->radii, a->depths, n_u32, w.dp_part,   \
+                           n_part, w.dp_ks, w.dp_tab, w.nb_p, sub);                                                                       \
+        hipLaunchKernelGGL(radix_scan_kernel, dim3((1 << B) * segs), dim3(SC_THREADS), 0, stream, w.dp_tab, w.nb_p, w.dp_totals, segs,    \
+                           seg_len);                                                                                                      \
+        hipLaunchKernelGGL(depth_part_scatter_kernel<B>, dim3(w.nb_p), dim3(DP_THREADS), 0, stream, a->radii, a->depths, n_u32, w.dp_ks,  \
+                           pairs_a, w.dp_tab, w.dp_totals, w.nb_p, segs, seg_len, w.n_ranked, w.dp_start, sub);                           \
+    } while (0)
+            const int bbits = dp_bbits(N);
+            switch (bbits) {
+                case 9: DNS_DEPTH_PARTITION(9); break;
+                case 10: DNS_DEPTH_PARTITION(10); break;
+                case 11: DNS_DEPTH_PARTITION(11); break;
+                default: DNS_DEPTH_PARTITION(12); break;
+            }
+#undef DNS_DEPTH_PARTITION
+            hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(1 << bbits), dim3(DP_THREADS), 0, stream, w.dp_ks, w.dp_start, pairs_a, pairs_b,
+                               w.val_a, fold ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
+        } else {
+            for (int pass = 0; pass < 4; ++pass) {
+                const int shift = 8 * pass;
+                const bool fold_here = fold && pass == 3;
+                // pass 0 knows its element count on the host (n_ptr = NULL), reads (radii, depths) instead of a key / value pair and drops
+                // the culled Gaussians; it leaves the number it kept in w.n_ranked, which bounds every later pass and the scans
+                if (rs_items_n(N) == RS_ITEMS_N_LARGE)
+                    radix_pass<uint32_t, RS_ITEMS_N_LARGE>(stream, ka, va, kb, vb, pass == 0 ? nullptr : w.n_ranked, n_u32, shift, 8, w.tab_n, w.totals,
+                                                           w.nb_n, nullptr, pass == 0 ? a->radii : nullptr, pass == 0 ? a->depths : nullptr, nullptr, 0,
+                                                           nullptr, nullptr, nullptr, pass == 0 ? w.n_ranked : nullptr,
+                                                           fold_here ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
+                else
+                    radix_pass<uint32_t, RS_ITEMS_N>(stream, ka, va, kb, vb, pass == 0 ? nullptr : w.n_ranked, n_u32, shift, 8, w.tab_n, w.totals,
+                                                     w.nb_n, nullptr, pass == 0 ? a->radii : nullptr, pass == 0 ? a->depths : nullptr, nullptr, 0,
+                                                     nullptr, nullptr, nullptr, pass == 0 ? w.n_ranked : nullptr,
+                                                     fold_here ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
+                uint32_t *t = ka; ka = kb; kb = t;
+                t = va; va = vb; vb = t;
+            }
         }
-        // after 4 passes the sorted order is back in val_a
+        // either way the depth order is in val_a now
         if (fold)
             hipLaunchKernelGGL(scan_sums_sorted_kernel, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.tiles_sorted, w.sums);
         else if (sorted_boxes)

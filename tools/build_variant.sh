@@ -19,6 +19,9 @@ $HIPCC $COMMON -fno-slp-vectorize -c $(src RASTER_BWD raster_bwd.hip) -o $O/rast
 $HIPCC $COMMON                   -c c_api.hip      -o $O/c_api.o & pids+=($!)
 $HIPCC $COMMON -ffp-contract=off -c postops.hip    -o $O/postops.o & pids+=($!)
 $HIPCC $COMMON                   -c losses.hip     -o $O/losses.o & pids+=($!)
+for f in pearson ags pointcloud metrics density levelset; do
+  $HIPCC $COMMON -ffp-contract=off -c $f.hip -o $O/$f.o & pids+=($!)
+done
 for p in "${pids[@]}"; do wait "$p"; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC $O/*.o -o ../../gpurun_ab/lib_$NAME.so
 rm -rf $O
