@@ -30,6 +30,8 @@ from . import density, torch_density  # noqa: F401
 from .density import GaussianDensityField, build_index, density_volume, install_density, knn  # noqa: F401
 from . import levelset, torch_levelset  # noqa: F401
 from .levelset import LevelSetCloud, export_level_set_points, install_level_sets, level_surface_points  # noqa: F401
+from . import marching, torch_marching  # noqa: F401
+from .marching import marching_cubes, marching_cubes_mesh, mcubes_marching_cubes  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -39,5 +41,6 @@ __all__ = [
     "local_pearson_depth", "ags_normal_loss", "ags_mesh_loss_fused", "export", "OrientedPointCloud",
     "export_oriented_points", "density", "torch_density", "GaussianDensityField", "build_index", "density_volume", "install_density", "knn",
     "levelset", "torch_levelset", "LevelSetCloud", "export_level_set_points", "install_level_sets", "level_surface_points",
+    "marching", "torch_marching", "marching_cubes", "marching_cubes_mesh", "mcubes_marching_cubes",
     "build_library", "load_library", "DnsplatError",
 ]

@@ -193,6 +193,14 @@ class LevelPointsArgs(ctypes.Structure):
     ]
 
 
+class McArgs(ctypes.Structure):
+    _fields_ = [
+        ("volume", c_void_p), ("nx", c_int32), ("ny", c_int32), ("nz", c_int32), ("level", c_float),
+        ("scratch", c_void_p), ("scratch_bytes", c_size_t), ("counts", c_void_p), ("cap_v", c_int64), ("cap_t", c_int64),
+        ("vertices", c_void_p), ("triangles", c_void_p), ("status", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -219,6 +227,8 @@ EXPORTS = [
     "dnsplat_density_eval",
     # likewise: the level-set surface points (the SuGaR ray search)
     "dnsplat_level_rays", "dnsplat_level_points",
+    # likewise: marching cubes on a lattice
+    "dnsplat_mc_scratch_bytes", "dnsplat_mc_count", "dnsplat_mc_emit",
 ]
 
 _lib = None
@@ -318,11 +328,15 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_density_eval.argtypes = [ctypes.POINTER(DensityArgs), c_void_p]
         L.dnsplat_level_rays.argtypes = [ctypes.POINTER(LevelRaysArgs), c_void_p]
         L.dnsplat_level_points.argtypes = [ctypes.POINTER(LevelPointsArgs), c_void_p]
+        L.dnsplat_mc_scratch_bytes.restype = c_size_t
+        L.dnsplat_mc_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
+        L.dnsplat_mc_count.argtypes = [ctypes.POINTER(McArgs), c_void_p]
+        L.dnsplat_mc_emit.argtypes = [ctypes.POINTER(McArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
                             "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
-                            "dnsplat_knn_index_bytes"):
+                            "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

@@ -12,7 +12,7 @@ dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rast
 get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
 
 One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
-``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
+``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``, ``_mc_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -413,6 +413,17 @@ def _level_points_args(width, height, depth, rgb, mask, indices, counts, intrins
     a.points, a.colors, a.normals = _ptr(points), _ptr(colors), _ptr(normals)
     a.capacity = points.shape[0]
     a.state, a.scratch = _ptr(state), _ptr(scratch)
+    return a
+
+
+def _mc_args(volume, level, scratch, counts, vertices=None, triangles=None, cap_v=0, cap_t=0, status=None):
+    a = McArgs()
+    a.volume, a.level = _ptr(volume), level
+    a.nx, a.ny, a.nz = volume.shape
+    a.scratch, a.scratch_bytes = _ptr(scratch), 0 if scratch is None else scratch.numel() * scratch.element_size()
+    a.counts = _ptr(counts)
+    a.cap_v, a.cap_t = cap_v, cap_t
+    a.vertices, a.triangles, a.status = _ptr(vertices), _ptr(triangles), _ptr(status)
     return a
 
 

@@ -59,7 +59,8 @@ extern "C" {
  * dnsplat_pointcloud_scratch_bytes: the oriented point cloud of the mesh exporter; dnsplat_eval_metrics / dnsplat_eval_metrics_args /
  * dnsplat_eval_metrics_scratch_bytes: the evaluation scores; dnsplat_knn_grid_dim / dnsplat_knn_index_bytes / dnsplat_knn_build /
  * dnsplat_knn_query / dnsplat_density_pack / dnsplat_density_eval / dnsplat_density_args: the Gaussian density field;
- * dnsplat_level_rays / dnsplat_level_points / dnsplat_level_rays_args / dnsplat_level_points_args: the level-set surface points). */
+ * dnsplat_level_rays / dnsplat_level_points / dnsplat_level_rays_args / dnsplat_level_points_args: the level-set surface points;
+ * dnsplat_mc_scratch_bytes / dnsplat_mc_count / dnsplat_mc_emit / dnsplat_mc_args: marching cubes on a lattice). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -831,6 +832,44 @@ typedef struct dnsplat_level_points_args {
 } dnsplat_level_points_args;
 int dnsplat_level_rays(const dnsplat_level_rays_args *args, dnsplat_stream_t stream);
 int dnsplat_level_points(const dnsplat_level_points_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ marching cubes (added after ABI 15, found by symbol)
+ * The step between the density lattice and the mesh of the reference's MarchingCubesMesh (export_mesh.py:778, mcubes.marching_cubes on
+ * the CPU there).  The output is a canonical, bit-reproducible function of (volume, level):
+ *   above      a lattice point is above iff v > level, one fp32 comparison (NaN is not above, +-inf behave as their values).
+ *   vertices   one per lattice edge whose two ends differ in that test.  The edge from point p along axis a belongs to p, the end
+ *              with the lower index; vertices are numbered in ascending (flat index of p, a).  Lattice coordinates, float32:
+ *              t = (level - v(p)) / (v(p + e_a) - v(p)), component a = float(p_a) + t, the other two are the integers; correctly
+ *              rounded, no contraction.  A non-finite t is written as the arithmetic gives it, a NaN as the quiet NaN 0x7FC00000.
+ *   triangles  int32 vertex ids.  Cells in ascending flat index of their lowest corner, within a cell in the order of the case table
+ *              (csrc/mc_table.h, generated by tools/gen_mc_table.py from contours traced on the cube's faces); the right-hand normal
+ *              points towards decreasing value.  A corner equal to `level` gives t = 0 or 1: the zero-area triangles are kept.
+ * volume is [nx,ny,nz] contiguous, the last axis fastest (meshgrid(indexing="ij"), as dnsplat_density_eval writes its lattice).
+ * dnsplat_mc_count — masks, counts and their scan into `scratch` (dnsplat_mc_scratch_bytes(nx, ny, nz) bytes); counts = {V, T}.  Four
+ *   launches.  The caller reads the two counts to size the buffers, or passes capacities it knows to suffice and reads nothing.
+ * dnsplat_mc_emit — after dnsplat_mc_count with the same volume, level, sizes, scratch and counts: the first min(V, cap_v) vertices and
+ *   min(T, cap_t) triangles; nothing is written past either capacity.  *status = DNSPLAT_MC_STATUS_VERTICES if V > cap_v, |
+ *   DNSPLAT_MC_STATUS_TRIANGLES if T > cap_t, else 0 (capacities above 2^31 - 1 count as 2^31 - 1: ids are int32).  Two launches.
+ * An axis shorter than 2 has no cells: counts = {0, 0}, status = 0, return 0, scratch may be NULL.  No atomics: equal inputs give equal
+ * bytes.  Returns without touching the device: DNSPLAT_ERR_INVALID_ARG for NULL args / volume / counts / scratch (/ status, / a buffer
+ * whose capacity is positive), a size < 1, nx ny nz >= 2^31 or a negative capacity; DNSPLAT_ERR_WORKSPACE for a short scratch. */
+#define DNSPLAT_MC_STATUS_VERTICES 1
+#define DNSPLAT_MC_STATUS_TRIANGLES 2
+typedef struct dnsplat_mc_args {
+    const float *volume;        /* device [nx,ny,nz] */
+    int32_t nx, ny, nz;
+    float level;
+    void *scratch;
+    size_t scratch_bytes;
+    int64_t *counts;            /* device int64 [2]: V, T; written by count, read by emit */
+    int64_t cap_v, cap_t;       /* emit: rows of vertices / triangles */
+    float *vertices;            /* emit: [cap_v,3] */
+    int32_t *triangles;         /* emit: [cap_t,3] */
+    int32_t *status;            /* emit: device int32 [1] */
+} dnsplat_mc_args;
+size_t dnsplat_mc_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);   /* 0 for an invalid size */
+int dnsplat_mc_count(const dnsplat_mc_args *args, dnsplat_stream_t stream);
+int dnsplat_mc_emit(const dnsplat_mc_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows

@@ -19,7 +19,7 @@ $HIPCC $COMMON -fno-slp-vectorize -c $(src RASTER_BWD raster_bwd.hip) -o $O/rast
 $HIPCC $COMMON                   -c c_api.hip      -o $O/c_api.o & pids+=($!)
 $HIPCC $COMMON -ffp-contract=off -c postops.hip    -o $O/postops.o & pids+=($!)
 $HIPCC $COMMON                   -c losses.hip     -o $O/losses.o & pids+=($!)
-for f in pearson ags pointcloud metrics density levelset; do
+for f in pearson ags pointcloud metrics density levelset marching; do
   $HIPCC $COMMON -ffp-contract=off -c $f.hip -o $O/$f.o & pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
