@@ -71,6 +71,72 @@ def smallest_rank_gap(points, queries, ranks=RANKS):
     return float(gap.min())
 
 
+def uniform_means(N, seed):
+    """float32 [N,3]: the means of ``field_inputs``' law alone, ``(rand(N,3) - 0.5) * 10``, for sizes at which its N x N scale
+    initialisation is out of reach."""
+    return ((torch.rand(N, 3, generator=torch.Generator().manual_seed(seed)) - 0.5) * 10).float().contiguous()
+
+
+# ---- the k-NN index (csrc/density_common.h, csrc/density.hip), restated in NumPy -------------------------------------------------------
+
+KNN_MAX_GRID = 128              # include/dnsplat.h DNSPLAT_KNN_MAX_GRID
+INDEX_HEADER_BYTES = 64         # density_common.h DfHeader
+
+
+def index_grid_dim(N, cap=KNN_MAX_GRID):
+    """df_grid_dim: the largest G with 2 G^3 <= N (about two points per cell), at least 1, at most ``cap``.  In integers."""
+    g = 1
+    while 2 * (g + 1) ** 3 <= N:
+        g += 1
+    return min(g, cap)
+
+
+def index_restatement(means):
+    """The part of the index buffer a query reads, for float32 means [N,3], written from the statements of density_common.h and
+    density.hip and not from their code: a dict with
+
+      G, C            cells per axis and G^3
+      lo, hi, inv_h   float32 [3]: the exact bounding box; inv_h = fl32(G / fl32(hi - lo)), 0 where the extent is 0 or infinite or the
+                      quotient overflows (the axis is one cell thick there)
+      g               int32 [3]: G where inv_h > 0, else 1
+      cell            int64 [N]: (c2 G + c1) G + c0 with c_a = t >= 0 ? int(min(t, g_a - 1)) : 0, t = fl32(fl32(p_a - lo_a) inv_h_a) —
+                      numpy's float32 operations round once each, as __fsub_rn and __fmul_rn do
+      cell_start      int32 [C + 1]: the exclusive prefix sum of the cell histogram, the last entry N
+      order           int64 [N]: the Gaussian indices in stable order of cell id (ascending index inside a cell)
+      bytes           uint8: the 64-byte header (its padding zero), cell_start padded with zeros to 16 bytes, then the rows
+                      (x, y, z, bits of index) in ``order``."""
+    p = np.ascontiguousarray(means.numpy() if torch.is_tensor(means) else means, dtype=np.float32)
+    N = p.shape[0]
+    G = index_grid_dim(N)
+    C = G ** 3
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    inv_h = np.zeros(3, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        ext = hi - lo
+        for a in range(3):
+            if ext[a] > 0 and np.isfinite(ext[a]):
+                q = np.float32(G) / ext[a]
+                inv_h[a] = q if np.isfinite(q) else 0.0
+        g = np.where(inv_h > 0, G, 1).astype(np.int32)
+        c = []
+        for a in range(3):
+            t = (p[:, a] - lo[a]) * inv_h[a]
+            assert t.dtype == np.float32
+            c.append(np.where(t >= 0, np.minimum(t, np.float32(g[a] - 1)), np.float32(0)).astype(np.int64))
+    cell = (c[2] * G + c[1]) * G + c[0]
+    cell_start = np.concatenate([[0], np.cumsum(np.bincount(cell, minlength=C))]).astype(np.int32)
+    order = np.argsort(cell, kind="stable")
+    at_sorted = (INDEX_HEADER_BYTES + 4 * (C + 1) + 15) // 16 * 16
+    raw = np.zeros(at_sorted + 16 * N, dtype=np.uint8)
+    raw[0:12], raw[12:24], raw[24:36], raw[36:48] = lo.view(np.uint8), hi.view(np.uint8), inv_h.view(np.uint8), g.view(np.uint8)
+    raw[INDEX_HEADER_BYTES:INDEX_HEADER_BYTES + 4 * (C + 1)] = cell_start.view(np.uint8)
+    rows = np.empty((N, 4), dtype=np.int32)
+    rows[:, :3] = p[order].view(np.int32)
+    rows[:, 3] = order
+    raw[at_sorted:] = rows.reshape(-1).view(np.uint8)
+    return dict(G=G, C=C, lo=lo, hi=hi, inv_h=inv_h, g=g, cell=cell, cell_start=cell_start, order=order, at_sorted=at_sorted, bytes=raw)
+
+
 def load_golden(path):
     g = np.load(path)
     t = {k: torch.from_numpy(g[k].astype(np.float32)) for k in ("means", "scales", "quats", "opacities", "samples")}
