@@ -1420,18 +1420,19 @@ __global__ __launch_bounds__(256) void visible_mask_kernel(int N, uint32_t capac
 }
 
 // launch 2: exclusive prefix sum of the block popcounts (one workgroup; 78 k words at 5 M Gaussians) + the total
-__global__ __launch_bounds__(1024) void visible_scan_kernel(int nblk, const uint32_t *__restrict__ counts, float *__restrict__ slab)
+constexpr int VIS_SCAN_THREADS = 1024;      // thread t sums, then numbers, the `per` consecutive block counts from t * per on
+__global__ __launch_bounds__(VIS_SCAN_THREADS) void visible_scan_kernel(int nblk, const uint32_t *__restrict__ counts, float *__restrict__ slab)
 {
-    __shared__ uint32_t part[1024];
+    __shared__ uint32_t part[VIS_SCAN_THREADS];
     uint32_t *hdr = reinterpret_cast<uint32_t *>(slab);
     uint32_t *offs = hdr + 8 + 2 * nblk;
-    const int per = (nblk + 1023) / 1024;
+    const int per = (nblk + VIS_SCAN_THREADS - 1) / VIS_SCAN_THREADS;
     const int b0 = threadIdx.x * per, b1 = min(nblk, b0 + per);
     uint32_t sum = 0;
     for (int b = b0; b < b1; ++b) sum += counts[b];
     part[threadIdx.x] = sum;
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
+    for (int d = 1; d < VIS_SCAN_THREADS; d <<= 1) {
         const uint32_t v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0u;
         __syncthreads();
         part[threadIdx.x] += v;
@@ -1439,7 +1440,7 @@ __global__ __launch_bounds__(1024) void visible_scan_kernel(int nblk, const uint
     }
     uint32_t run = part[threadIdx.x] - sum;
     for (int b = b0; b < b1; ++b) { offs[b] = run; run += counts[b]; }
-    if (threadIdx.x == 1023) hdr[0] = part[1023];
+    if (threadIdx.x == VIS_SCAN_THREADS - 1) hdr[0] = part[VIS_SCAN_THREADS - 1];
 }
 
 }  // namespace
@@ -1695,7 +1696,7 @@ extern "C" int dnsplat_visible_index(int32_t N, int32_t capacity, const int32_t 
     hipLaunchKernelGGL(visible_mask_kernel, dim3((N + 256) / 256), dim3(256), 0, (hipStream_t)stream, N, (uint32_t)capacity, radii, viewmat,
                        slab, scratch);
     DNS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(visible_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, nblk, scratch, slab);
+    hipLaunchKernelGGL(visible_scan_kernel, dim3(1), dim3(VIS_SCAN_THREADS), 0, (hipStream_t)stream, nblk, scratch, slab);
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
 }

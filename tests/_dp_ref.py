@@ -1,7 +1,8 @@
 """Torch restatements of the exchange step's HIP kernels for the CPU (gloo) tests — test infrastructure, as the oracle is:
 the packed (visible rows only) colour-gradient slab of include/dnsplat.h (dnsplat_visible_index + dnsplat_proj_grads.sh_packed) and the
-rebuild / add kernels (dnsplat_sh_grads_from_factors, _add_factors, _from_packed).  tests/test_gpu_parity.py compares the kernels
-with the same arithmetic on the GPU."""
+rebuild / add kernels (dnsplat_sh_grads_from_factors, _add_factors, _from_packed).  tests/test_gpu_sh_exchange.py compares the kernels
+with these restatements on the GPU — the slabs as bytes, the rebuilt rows per Gaussian against ``rebuild_ref64`` — and
+tests/test_sh_exchange_reference.py holds the restatements themselves (against autograd, and the inputs' conditioning) without one."""
 import torch
 
 
@@ -71,3 +72,152 @@ def make_rebuild_ref(dense_ref):
             v_shN.copy_(tot[:, 1:])
 
     return rebuild_ref
+
+
+# ---- the rebuild per row (tests/test_sh_exchange_reference.py, tests/test_gpu_sh_exchange.py) --------------------------------------------
+
+U24 = 2.0 ** -24
+# How far a plain fp32 restatement of the rebuild (``rebuild_ref(..., dtype=torch.float32)``) lies from ``rebuild_ref64``, as the worst
+# ratio of ||row error||_2 to 2^-24 ||A_row||_2 over every case of ``EXCHANGE_CASES`` x degrees 0 .. 3 x every form — measured on the CPU
+# and asserted by test_sh_exchange_reference.py (the inputs are benign) — and the bound the kernels are held to: four times that, rounded
+# up.  The kernel differs from the restatement by `1.f / sqrtf` and by nothing else that is more than a few roundings (project.hip is
+# compiled without FMA contraction).
+CPU_RATIO = 5.2
+KAPPA = 21
+
+#   (N, views): the sizes of the rebuild cases — one Gaussian, one short of / exactly / one past a 64-row workgroup, many workgroups with
+#   a short last one, and (packed only) 1025 mask words in front of the offsets
+EXCHANGE_CASES = ((1, 3), (63, 3), (64, 3), (65, 3), (10_007, 3))
+EXCHANGE_BIG = (65_537, 2)
+
+_SH = (0.2820947917738781, 0.48860251190292, 1.092548430592079, 0.5462742152960395, 0.9461746957575601, 0.3153915652525201,
+       2.285228997322329, 0.4570457994644658, 1.445305721320277, 0.5900435899266435, 1.865881662950577, 1.119528997770346)
+
+
+def sh_basis_ref(degree: int, d: torch.Tensor, absolute: bool = False) -> torch.Tensor:
+    """[..., 3] unit directions -> [..., 16] real SH basis in d's dtype, the operations of project.hip's sh_basis in their order; bands
+    above ``degree`` are zero.  ``absolute``: every monomial of every polynomial in absolute value (the magnitude roundings act on)."""
+    x, y, z = d.unbind(-1)
+    m = -1.0
+    if absolute:
+        x, y, z, m = x.abs(), y.abs(), z.abs(), 1.0
+    c0, c1, c2b, c2a, c2c, c2d, c3a, c3b, c3c, c3d, c3e, c3f = _SH
+    bas = [torch.full_like(x, c0)]
+    if degree >= 1:
+        bas += [(m * c1) * y, c1 * z, (m * c1) * x]
+    if degree >= 2:
+        z2 = z * z
+        t0b = (m * c2b) * z
+        fc1 = x * x + m * (y * y)
+        fs1 = 2.0 * x * y
+        bas += [c2a * fs1, t0b * y, c2c * z2 + m * c2d, t0b * x, c2a * fc1]
+    if degree >= 3:
+        t0c = (m * c3a) * z2 + c3b
+        t1b = c3c * z
+        fc2 = x * fc1 + m * (y * fs1)
+        fs2 = x * fs1 + y * fc1
+        bas += [(m * c3d) * fs2, t1b * fs1, t0c * y, z * (c3e * z2 + m * c3f), t0c * x, t1b * fc1, (m * c3d) * fc2]
+    bas += [torch.zeros_like(x)] * (16 - len(bas))
+    return torch.stack(bas, -1)
+
+
+def rebuild_ref(cols: torch.Tensor, pos: torch.Tensor, means: torch.Tensor, degree: int, scale: float, skip_view: int = -1,
+                own: torch.Tensor = None, dtype=torch.float64):
+    """``cols`` [w,N,3], ``pos`` [w,3], ``means`` [N,3] (float32, taken as exact) -> (rows [N,16,3], A [N,16,3]) in closed form:
+    rows = scale sum_v Y(d_v) (x) cols_v with d_v = normalize(means - pos_v), the views in order, ``skip_view`` left out, ``own``
+    ([N,16,3], the add form) added last; computed in ``dtype``.  A (always float64) = |scale| sum_v Ybar(d_v) (x) |cols_v|, plus
+    |own + rows| in the add form: the magnitude the kernel's roundings act on."""
+    w, n = cols.shape[:2]
+    acc = torch.zeros(n, 16, 3, dtype=dtype)
+    mag = torch.zeros(n, 16, 3, dtype=torch.float64)
+    for v in range(w):
+        if v == skip_view:
+            continue
+        delta = means.to(dtype) - pos[v].to(dtype)
+        inorm = 1.0 / torch.sqrt(delta[:, 0] * delta[:, 0] + delta[:, 1] * delta[:, 1] + delta[:, 2] * delta[:, 2])
+        d = delta * inorm[:, None]
+        acc += sh_basis_ref(degree, d)[:, :, None] * cols[v].to(dtype)[:, None, :]
+        d64 = torch.nn.functional.normalize(means.double() - pos[v].double(), dim=-1)
+        mag += sh_basis_ref(degree, d64, absolute=True)[:, :, None] * cols[v].double().abs()[:, None, :]
+    rows = torch.tensor(scale, dtype=dtype) * acc
+    mag *= abs(scale)
+    if own is not None:
+        rows = own.to(dtype) + rows
+        mag = mag + rows.double().abs()
+    return rows, mag
+
+
+def rebuild_ref64(cols, pos, means, degree, scale, skip_view=-1, own=None):
+    return rebuild_ref(cols, pos, means, degree, scale, skip_view, own, torch.float64)
+
+
+def row_ratio(got: torch.Tensor, ref: torch.Tensor, mag: torch.Tensor, degree: int):
+    """[N,K,3] rows against the float64 ones -> (worst ||got - ref||_2 / (2^-24 ||A||_2) over the rows with A != 0 — over the active bands
+    k < (degree + 1)^2, the others are compared as bits by the callers — and the number of rows with A == 0 that are not exactly ref)."""
+    nb = (degree + 1) ** 2
+    k = min(nb, got.shape[1])
+    err = (got[:, :k].double() - ref[:, :k]).reshape(got.shape[0], -1).norm(dim=1)
+    a = mag[:, :k].reshape(got.shape[0], -1).norm(dim=1)
+    live = a > 0
+    ratio = float((err[live] / (U24 * a[live])).max()) if bool(live.any()) else 0.0
+    return ratio, int((err[~live] != 0).sum())
+
+
+def exchange_inputs(n: int, w: int, seed: int = 0):
+    """Synthetic inputs of the rebuild: means in a box of half side 4, ``w`` camera centres on the sphere of radius 9 (so every
+    |mean - pos| >= 9 - 4 sqrt 3 > 2), a visibility mask of about 78 %, colour gradients whose magnitudes span three decades (a dim
+    Gaussian beside a bright one), zero where invisible, at a further 5 % of the visible (v, g), and in EVERY view for the Gaussians
+    with g % 11 == 5: about 30 % of (v, g) exactly zero.  -> dict(means [n,3], pos [w,3], vis bool [w,n], cols [w,n,3]), float32."""
+    g = torch.Generator().manual_seed(7700 + 31 * seed + n % 9973 + 1000 * w)
+    means = ((torch.rand(n, 3, generator=g) - 0.5) * 8).float()
+    pos = (torch.nn.functional.normalize(torch.randn(w, 3, generator=g), dim=-1) * 9).float()
+    dead = (torch.arange(n) % 11) == 5
+    vis = (torch.rand(w, n, generator=g) > 0.22) & ~dead
+    cols = torch.randn(w, n, 3, generator=g) * torch.pow(10.0, -3 * torch.rand(w, n, 1, generator=g))
+    cols = cols * (vis & (torch.rand(w, n, generator=g) > 0.05))[..., None]
+    assert float((means[None] - pos[:, None]).double().norm(dim=-1).min()) >= 1.0
+    return dict(means=means.contiguous(), pos=pos.contiguous(), vis=vis, cols=cols.float().contiguous())
+
+
+def dense_slabs(cols: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """[w,N,3], [w,3] -> [w, 3 N + 4]: the slabs dnsplat_sh_factors writes."""
+    w = cols.shape[0]
+    return torch.cat([cols.reshape(w, -1), pos, torch.zeros(w, 1)], -1).float().contiguous()
+
+
+def packed_slabs(cols: torch.Tensor, vis: torch.Tensor, pos: torch.Tensor, capacity: int) -> torch.Tensor:
+    return torch.stack([pack_slab_ref(cols[v], vis[v], pos[v], capacity) for v in range(cols.shape[0])]).contiguous()
+
+
+def overflow_capacity(vis: torch.Tensor) -> int:
+    """One row less than the fullest view holds: that view overflows."""
+    return max(int(vis.sum(1).max()) - 1, 0)
+
+
+def own_rows(cols, pos, means, degree, scale, view, K=16):
+    """The rows view ``view``'s own projection backward leaves for the add form: its share, in float32, in the active bands; a
+    recognisable pattern of positive floats in the others (which the add form must leave as they are)."""
+    share, _ = rebuild_ref64(cols[view:view + 1], pos[view:view + 1], means, degree, scale)
+    n = means.shape[0]
+    pattern = 1000.0 + (torch.arange(n * 16 * 3) % 977).float().reshape(n, 16, 3)
+    active = (torch.arange(16) < (degree + 1) ** 2)[None, :, None]
+    return torch.where(active, share.float(), pattern)
+
+
+def exchange_forms(inp, packed_only: bool = False):
+    """The forms one set of inputs is run in: (name, skip_view, capacity or None for dense slabs, the colours the reference reads).
+    Dense rebuild and dense add with every skip_view; the same over packed slabs with room for every view's rows (same colours: they are
+    zero where invisible) and with one row too few for the fullest view (the colours ``unpack_slab_ref`` gives back: the same rows
+    dropped)."""
+    w, n = inp["cols"].shape[:2]
+    roomy = int(inp["vis"].sum(1).max())
+    tight = overflow_capacity(inp["vis"])
+    over = packed_slabs(inp["cols"], inp["vis"], inp["pos"], tight)
+    kept = torch.stack([unpack_slab_ref(over[v], n, tight)[0] for v in range(w)])
+    forms = []
+    for name, cap, cols in (("dense", None, inp["cols"]), ("packed", roomy, inp["cols"]), ("packed_overflow", tight, kept)):
+        if packed_only and cap is None:
+            continue
+        forms.append((name, -1, cap, cols))
+        forms += [(f"{name}_add_skip{s}", s, cap, cols) for s in range(w)]
+    return forms

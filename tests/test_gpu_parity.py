@@ -1045,7 +1045,7 @@ def test_sh_factor_exchange_rebuilds_the_multi_camera_gradient(dns, layout, defe
             gp_f, sh_f = one(c, ex)
             assert ex.meta is None
             assert_close(sh_f.grad, dense[i][1].grad, "cat layout ignores the factor exchange", 1e-6)
-        # the rebuild kernel itself still supports the [N,16,3] destination
+        # the rebuild kernel itself still supports the [N,16,3] destination: tests/test_gpu_sh_exchange.py runs it there
         return
     factors = []
     for c in cams:
@@ -1059,42 +1059,28 @@ def test_sh_factor_exchange_rebuilds_the_multi_camera_gradient(dns, layout, defe
     fac = torch.stack(factors).contiguous()
     assert fac.shape == (3, 3 * N + 4)                 # one slab per camera: [N,3] colour gradients | camera position | pad
     means_dev = gp0["means"].detach().to(DEV).contiguous()
-    if layout == "split":
-        v0 = torch.empty(N, 3, device=DEV)
-        vN = torch.empty(N, 15, 3, device=DEV)
-        _lib.check(_lib.lib().dnsplat_sh_grads_from_factors(N, 3, _ops._ptr(fac), _ops._ptr(means_dev), 3, 16, 1.0 / 3, _ops._ptr(v0), 3,
-                                                            _ops._ptr(vN), 45, _ops._stream()), "dnsplat_sh_grads_from_factors")
-        ref0 = sum(d[0]["features_dc"].grad for d in dense) / 3
-        refN = sum(d[0]["features_rest"].grad for d in dense) / 3
-        assert_close(v0, ref0, "rebuilt features_dc gradient", 1e-5)
-        assert_close(vN, refN, "rebuilt features_rest gradient", 1e-5)
-    else:
-        vc = torch.empty(N, 16, 3, device=DEV)
-        _lib.check(_lib.lib().dnsplat_sh_grads_from_factors(N, 3, _ops._ptr(fac), _ops._ptr(means_dev), 3, 16, 1.0 / 3, _ops._ptr(vc), 48,
-                                                            _ops._ptr(vc.view(-1)[3:]), 48, _ops._stream()),
-                   "dnsplat_sh_grads_from_factors")
-        ref = sum(d[1].grad for d in dense) / 3
-        assert_close(vc, ref, "rebuilt SH coefficient gradient", 1e-5)
+    v0 = torch.empty(N, 3, device=DEV)
+    vN = torch.empty(N, 15, 3, device=DEV)
+    _lib.check(_lib.lib().dnsplat_sh_grads_from_factors(N, 3, _ops._ptr(fac), _ops._ptr(means_dev), 3, 16, 1.0 / 3, _ops._ptr(v0), 3,
+                                                        _ops._ptr(vN), 45, _ops._stream()), "dnsplat_sh_grads_from_factors")
+    ref0 = sum(d[0]["features_dc"].grad for d in dense) / 3
+    refN = sum(d[0]["features_rest"].grad for d in dense) / 3
+    assert_close(v0, ref0, "rebuilt features_dc gradient", 1e-5)
+    assert_close(vN, refN, "rebuilt features_rest gradient", 1e-5)
     # the single-rank exchange (what DNSPLAT_FORCE_DIST=1 exercises with RCCL) reproduces the dense gradient
     gp_1, sh_1 = one(cams[0], ex)
-    if layout == "split":
-        assert ex.finish(v_sh0=gp_1["features_dc"].grad, v_shN=gp_1["features_rest"].grad) == 0
-    else:
-        assert ex.finish(v_coeffs=sh_1.grad) == 0
+    assert ex.finish(v_sh0=gp_1["features_dc"].grad, v_shN=gp_1["features_rest"].grad) == 0
     torch.cuda.synchronize()
-    if layout == "split":
-        assert_close(gp_1["features_rest"].grad, dense[0][0]["features_rest"].grad, "single-rank exchange", 1e-6)
-        assert_close(gp_1["features_dc"].grad, dense[0][0]["features_dc"].grad, "single-rank exchange dc", 1e-6)
-        # the default exchange at world 1: own rows — dnsplat_project_bwd writes the complete rows, finish() launches nothing
-        ex1 = dp.ShFactorExchange()
-        ex1.deferred = deferred
-        gp_2, _ = one(cams[0], ex1)
-        assert ex1.use_own_rows() and ex1.finish(v_sh0=gp_2["features_dc"].grad, v_shN=gp_2["features_rest"].grad) == 0
-        torch.cuda.synchronize()
-        assert torch.equal(gp_2["features_rest"].grad, dense[0][0]["features_rest"].grad), "own rows at world 1 != the single-GPU rows"
-        assert torch.equal(gp_2["features_dc"].grad, dense[0][0]["features_dc"].grad)
-    else:
-        assert_close(sh_1.grad, dense[0][1].grad, "single-rank exchange", 1e-6)
+    assert_close(gp_1["features_rest"].grad, dense[0][0]["features_rest"].grad, "single-rank exchange", 1e-6)
+    assert_close(gp_1["features_dc"].grad, dense[0][0]["features_dc"].grad, "single-rank exchange dc", 1e-6)
+    # the default exchange at world 1: own rows — dnsplat_project_bwd writes the complete rows, finish() launches nothing
+    ex1 = dp.ShFactorExchange()
+    ex1.deferred = deferred
+    gp_2, _ = one(cams[0], ex1)
+    assert ex1.use_own_rows() and ex1.finish(v_sh0=gp_2["features_dc"].grad, v_shN=gp_2["features_rest"].grad) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(gp_2["features_rest"].grad, dense[0][0]["features_rest"].grad), "own rows at world 1 != the single-GPU rows"
+    assert torch.equal(gp_2["features_dc"].grad, dense[0][0]["features_dc"].grad)
 
 
 @pytest.mark.parametrize("packed", [False, True])
