@@ -14,6 +14,7 @@
 //                          a fill value), the neighbours either the caller's index tensor or the search run in the same thread.
 // Both neighbour sources feed df_accumulate in rank order, and the file is compiled without contraction: they give equal bits.
 
+#include "block_scan.h"
 #include "density_common.h"
 
 namespace {
@@ -106,40 +107,7 @@ __global__ __launch_bounds__(DF_THREADS) void df_cell_kernel(int N, const float 
 // counts[0 .. n) -> their exclusive prefix sums in place (n = C + 1: the last entry becomes N)
 __global__ __launch_bounds__(DF_SCAN_THREADS) void df_scan_kernel(long long n, int32_t *__restrict__ counts)
 {
-    __shared__ int wave_tot[DF_SCAN_THREADS / DNS_WAVE];
-    const int t = threadIdx.x, lane = t & (DNS_WAVE - 1), wave = t / DNS_WAVE;
-    int carry = 0;
-    for (long long i0 = 0; i0 < n; i0 += DF_SCAN_THREADS * DF_SCAN_PER) {
-        const long long i = i0 + (long long)t * DF_SCAN_PER;
-        int v[DF_SCAN_PER], sum = 0;
-#pragma unroll
-        for (int j = 0; j < DF_SCAN_PER; ++j) {
-            v[j] = i + j < n ? counts[i + j] : 0;
-            sum += v[j];
-        }
-        int inc = sum;
-#pragma unroll
-        for (int off = 1; off < DNS_WAVE; off <<= 1) {
-            const int o = __shfl_up(inc, off, DNS_WAVE);
-            if (lane >= off) inc += o;
-        }
-        __syncthreads();                                           // the previous round's readers are done with wave_tot
-        if (lane == DNS_WAVE - 1) wave_tot[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < DF_SCAN_THREADS / DNS_WAVE; ++w) {
-            const int c = wave_tot[w];
-            if (w < wave) before += c;
-            total += c;
-        }
-        int run = carry + before + inc - sum;
-#pragma unroll
-        for (int j = 0; j < DF_SCAN_PER; ++j) {
-            if (i + j < n) counts[i + j] = run;
-            run += v[j];
-        }
-        carry += total;
-    }
+    dns_scan_in_place<DF_SCAN_THREADS, DF_SCAN_PER>(n, counts);
 }
 
 __global__ __launch_bounds__(DF_THREADS) void df_scatter_kernel(int N, const int32_t *__restrict__ cell_of, const int32_t *__restrict__ cell_start,

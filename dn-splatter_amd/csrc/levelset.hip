@@ -6,7 +6,8 @@
 //   dnsplat_level_rays     one launch.  Per pixel i = v W + u:
 //                            d = mask && !mask[i] ? 0 : depth[i]; d <= 0 takes no part; a non-finite d (or point) takes no part either
 //                            and reads nothing — our choice, the reference would raise inside sklearn;
-//                            p = the world point of dnsplat_backproject_points, bit-equal; o = c2w[:3, 3]; dir = (p - o) / max(|p - o|, 1e-12);
+//                            p = the world point of dnsplat_backproject_points, the same code (pixel_camera.h); o = c2w[:3, 3];
+//                            dir = (p - o) / max(|p - o|, 1e-12);
 //                            the neighbours of p: ranks 1 .. 16 of 17 (knn_sk drops the nearest; kept), df_search in the thread or the
 //                            caller's [P,16] tensor; c = the first of them;
 //                            std = | exp(s_c) * (R(q_c / |q_c|)^T w) |, w = (o - mu_c) / |o - mu_c|;
@@ -18,8 +19,8 @@
 //   dnsplat_level_points   per level, one thread per selected row: x = p + t dir, colour, normal (row c of the model's normals, or
 //                          -normalize(sum_k w_k M_k M_k^T (x - mu_k)) with w_k the neighbour's density term, the search run again for
 //                          these rows only), the crop-box test, and the ordered append behind a device cursor (count per 256 rows,
-//                          one-workgroup scan that also moves the cursor, then the same rows again with the write), as
-//                          dnsplat_backproject_points appends.
+//                          one-workgroup scan that also moves the cursor, then the same rows again with the write): the append
+//                          of dnsplat_backproject_points, the same code (block_scan.h).
 // A DELIBERATE DEPARTURE from dn_model.py's arithmetic, which is fp32 throughout: (1) x_j is never formed.  The evaluation is handed
 // the offset (p - mu_k) + (r_j std) dir, each term of the size of the Gaussian; rounding p + (r_j std) dir to an ulp of |p| first
 // costs, through M, more than the whole evaluation does (the reference's own densities are 1.3e-5 from their fp64 values for it).
@@ -29,7 +30,9 @@
 // No atomic anywhere; compiled without contraction.  Both neighbour sources feed the same code after the LDS column is filled, and the
 // two lane mappings differ only in which thread takes which pixel: equal bits in all four combinations.
 
+#include "block_scan.h"
 #include "density_common.h"
+#include "pixel_camera.h"
 
 namespace {
 
@@ -42,30 +45,19 @@ constexpr int LS_TILE = 8;                            // a wave's block of pixel
 
 static_assert(LS_TILE * LS_TILE == DNS_WAVE, "one lane per pixel of a block");
 
-struct LsCam {
-    int W, H;
-    long long P;
-    const float *depth;
-    const uint8_t *mask;
-    float fx, fy, cx, cy;
-    const float *xform;
-};
+using LsCam = DnsPixelCamera;
 
 // the world point of pixel i and the unit ray direction through it; false: the pixel takes no part (nothing else was read)
 __device__ __forceinline__ bool ls_point(const LsCam &c, long long i, float p[3], float dir[3])
 {
-    const float d = (c.mask && !c.mask[i]) ? 0.f : c.depth[i];
+    const float d = dns_pixel_depth(c, i);
     if (!(d > 0.f) || !(d < INFINITY)) return false;
-    const int v = (int)(i / c.W), u = (int)(i - (long long)v * c.W);
-    // pointcloud.hip pc_row: (coords - c) * depth / f, the pixel centre at + 0.5
-    const float px = __fdiv_rn(__fmul_rn(__fsub_rn((float)u + 0.5f, c.cx), d), c.fx);
-    const float py = __fdiv_rn(__fmul_rn(__fsub_rn((float)v + 0.5f, c.cy), d), c.fy);
-    const float *A = c.xform, *T = c.xform + 9;
+    dns_pixel_point(c, i, d, p);
+    const float *T = c.xform + 9;
     double e[3];
     bool finite = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        p[a] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(px, A[a]), __fmul_rn(py, A[3 + a])), __fmul_rn(d, A[6 + a])), T[a]);
         e[a] = (double)p[a] - (double)T[a];
         finite = finite && fabsf(p[a]) < INFINITY;
     }
@@ -252,64 +244,6 @@ struct LsPoints {
     const float *records;
 };
 
-// the number of threads before the caller (in thread order) whose flag is set; total = the number in the whole workgroup
-__device__ __forceinline__ int ls_block_rank(bool flag, int *wave_tot, int &total)
-{
-    const int lane = threadIdx.x & (DNS_WAVE - 1), wave = threadIdx.x / DNS_WAVE;
-    const uint64_t b = dns_ballot(flag);
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < LS_WAVES; ++w) {
-        const int n = wave_tot[w];
-        if (w < wave) before += n;
-        total += n;
-    }
-    return before + below;
-}
-
-// One workgroup: counts[0 .. nb) -> their exclusive prefix sums in place; base[0] = the cursor before this call; the cursor moves by
-// the total, up to capacity; beyond it the overflow word is set (pointcloud.hip's append)
-__global__ __launch_bounds__(LS_THREADS) void ls_scan_kernel(int nb, int32_t *__restrict__ counts, int64_t capacity, int64_t *__restrict__ state,
-                                                              int64_t *__restrict__ base)
-{
-    __shared__ int wave_tot[LS_WAVES];
-    const int t = threadIdx.x, lane = t & (DNS_WAVE - 1), wave = t / DNS_WAVE;
-    int carry = 0;
-    for (int i0 = 0; i0 < nb; i0 += LS_THREADS) {
-        const int i = i0 + t;
-        const int v = i < nb ? counts[i] : 0;
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < DNS_WAVE; off <<= 1) {
-            const int o = __shfl_up(inc, off, DNS_WAVE);
-            if (lane >= off) inc += o;
-        }
-        __syncthreads();                                   // the previous round's readers are done with wave_tot
-        if (lane == DNS_WAVE - 1) wave_tot[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < LS_WAVES; ++w) {
-            const int n = wave_tot[w];
-            if (w < wave) before += n;
-            total += n;
-        }
-        if (i < nb) counts[i] = carry + before + inc - v;
-        carry += total;
-    }
-    if (t == 0) {
-        const int64_t at = state[0];
-        base[0] = at;
-        const int64_t end = at + (int64_t)carry;
-        state[0] = end > capacity ? (at > capacity ? at : capacity) : end;
-        if (end > capacity) state[1] = 1;
-    }
-}
-
 // one neighbour of the analytical normal at x = p + t dir: g += w M (M^T (x - mu)), w = o exp(-clamp(|M^T (x - mu)|^2, 0, 1e8) / 2),
 // x - mu formed as the ray kernel forms it, (p - mu) + t dir
 __device__ __forceinline__ void ls_grad_term(const float *__restrict__ records, int gi, const float p[3], float t, const float dir[3], float g[3])
@@ -343,19 +277,11 @@ __global__ __launch_bounds__(LS_THREADS) void ls_points_kernel(LsPoints f, int32
             keep = t == t;                                              // nan: an empty pixel
 #pragma unroll
             for (int a = 0; a < 3; ++a) x[a] = p[a] + t * dir[a];
-            if (keep && f.crop) {
-                const float *B = f.crop, *h = f.crop + 12;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const float q = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(B[4 * a], x[0]), __fmul_rn(B[4 * a + 1], x[1])), __fmul_rn(B[4 * a + 2], x[2])),
-                                              B[4 * a + 3]);
-                    keep = keep && fabsf(q) < h[a];                      // strict on both faces; a nan coordinate is outside
-                }
-            }
+            if (keep && f.crop) keep = dns_in_crop_box(f.crop, x);
         }
     }
     int total;
-    const int rank = ls_block_rank(keep, wave_tot, total);
+    const int rank = dns_block_rank<LS_THREADS>(keep, wave_tot, total);
     if (!WRITE) {
         if (threadIdx.x == 0) counts[blockIdx.x] = total;
         return;
@@ -404,10 +330,7 @@ extern "C" int dnsplat_level_rays(const dnsplat_level_rays_args *a, dnsplat_stre
     const long long P = (long long)a->width * a->height;
     if (P > 0x7fffffffLL) return DNSPLAT_ERR_UNSUPPORTED;
     LsRays e;
-    e.cam.W = a->width; e.cam.H = a->height; e.cam.P = P;
-    e.cam.depth = a->depth; e.cam.mask = a->mask;
-    e.cam.fx = a->fx; e.cam.fy = a->fy; e.cam.cx = a->cx; e.cam.cy = a->cy;
-    e.cam.xform = a->xform;
+    e.cam = dns_pixel_camera(*a);
     e.N = a->N;
     const bool search = a->neighbors == nullptr;
     if (search) e.ix = df_view(a->index, df_layout(a->N));
@@ -451,10 +374,7 @@ extern "C" int dnsplat_level_points(const dnsplat_level_points_args *a, dnsplat_
     if (P > 0x7fffffffLL) return DNSPLAT_ERR_UNSUPPORTED;
     if (a->n_rows == 0) return DNSPLAT_OK;
     LsPoints f;
-    f.cam.W = a->width; f.cam.H = a->height; f.cam.P = P;
-    f.cam.depth = a->depth; f.cam.mask = a->mask;
-    f.cam.fx = a->fx; f.cam.fy = a->fy; f.cam.cx = a->cx; f.cam.cy = a->cy;
-    f.cam.xform = a->xform;
+    f.cam = dns_pixel_camera(*a);
     f.rgb = a->rgb; f.indices = a->indices; f.counts = a->counts; f.n_rows = a->n_rows;
     f.crop = a->crop; f.t_hit = a->t_hit; f.closest = a->closest; f.mode = a->normal_mode; f.gauss_normals = a->gauss_normals;
     f.N = a->N; f.records = a->records;
@@ -466,7 +386,7 @@ extern "C" int dnsplat_level_points(const dnsplat_level_points_args *a, dnsplat_
     int32_t *block_counts = (int32_t *)((char *)a->scratch + 16);
     hipLaunchKernelGGL((ls_points_kernel<false>), dim3(nb), dim3(LS_THREADS), 0, stream, f, block_counts, (const int64_t *)base, a->capacity,
                        a->points, a->colors, a->normals, a->state);
-    hipLaunchKernelGGL(ls_scan_kernel, dim3(1), dim3(LS_THREADS), 0, stream, nb, block_counts, a->capacity, a->state, base);
+    hipLaunchKernelGGL(dns_append_scan_kernel<LS_THREADS>, dim3(1), dim3(LS_THREADS), 0, stream, nb, block_counts, a->capacity, a->state, base);
     hipLaunchKernelGGL((ls_points_kernel<true>), dim3(nb), dim3(LS_THREADS), 0, stream, f, block_counts, (const int64_t *)base, a->capacity,
                        a->points, a->colors, a->normals, a->state);
     DNS_CHECK_LAUNCH();

@@ -26,7 +26,7 @@
 // nothing is left (up to 64 rounds on random images) doubles the call.
 // Traffic: 56 B per pixel read once, plus 24 B per pixel for each of rounds two and three.
 
-#include "splat_common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -279,21 +279,11 @@ __device__ __forceinline__ bool mt_find_bin(const unsigned long long *__restrict
 {
     constexpr int PER = BINS / MT_THREADS;
     __shared__ unsigned long long wave_sum[MT_WAVES];
-    const int t = threadIdx.x, lane = t & (DNS_WAVE - 1), wave = t / DNS_WAVE;
-    unsigned long long c[PER], mine = 0ull;
+    const int t = threadIdx.x;
+    unsigned long long c[PER], mine = 0ull, all;
 #pragma unroll
     for (int k = 0; k < PER; ++k) { c[k] = hist[t * PER + k]; mine += c[k]; }
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int off = 1; off < DNS_WAVE; off <<= 1) {
-        const unsigned long long up = __shfl_up(incl, off, DNS_WAVE);
-        if (lane >= off) incl += up;
-    }
-    if (lane == DNS_WAVE - 1) wave_sum[wave] = incl;
-    __syncthreads();
-    unsigned long long before = incl - mine;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    __syncthreads();                                                             // wave_sum may be used again by the next call
+    const unsigned long long before = dns_block_scan<MT_THREADS>(mine, wave_sum, all);
     if (rank < before || rank >= before + mine) return false;
     unsigned long long cum = before;
 #pragma unroll

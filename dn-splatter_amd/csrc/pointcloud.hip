@@ -17,7 +17,8 @@
 // No atomic anywhere and no sum whose order depends on scheduling: equal inputs (and seed) give equal bits.  Compiled without
 // contraction: every product and sum below is the single fp32 operation torch performs.
 
-#include "splat_common.h"
+#include "block_scan.h"
+#include "pixel_camera.h"
 
 namespace {
 
@@ -32,83 +33,15 @@ constexpr float PC_EPS = 1e-6f;                          // find_depth_edges: 1 
 
 static_assert(PC_TH * PC_TW == PC_THREADS, "one thread per (row, word) of a dilation tile");
 
-// ---- ranks within a workgroup --------------------------------------------------------------------------------------------------------
+// ---- the sampler's scan -------------------------------------------------------------------------------------------------------------
 
-// the number of threads before the caller (in thread order) whose flag is set; total = the number in the whole workgroup
-__device__ __forceinline__ int pc_block_rank(bool flag, int *wave_tot, int &total)
+// One workgroup turns counts[0 .. nb) into their exclusive prefix sums in place and hands the total on: words = {n, min(k, n)}
+__global__ __launch_bounds__(PC_THREADS) void pc_scan_kernel(int nb, int32_t *__restrict__ counts, int32_t k, int32_t *__restrict__ words)
 {
-    const int lane = threadIdx.x & (DNS_WAVE - 1), wave = threadIdx.x / DNS_WAVE;
-    const uint64_t b = dns_ballot(flag);
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();                                      // the previous round's readers are done with wave_tot
-    if (lane == 0) wave_tot[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < PC_WAVES; ++w) {
-        const int c = wave_tot[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    return before + below;
-}
-
-// exclusive prefix sum of v over the threads of the workgroup
-__device__ __forceinline__ int pc_block_scan(int v, int *wave_tot, int &total)
-{
-    const int lane = threadIdx.x & (DNS_WAVE - 1), wave = threadIdx.x / DNS_WAVE;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < DNS_WAVE; off <<= 1) {
-        const int o = __shfl_up(inc, off, DNS_WAVE);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();
-    if (lane == DNS_WAVE - 1) wave_tot[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < PC_WAVES; ++w) {
-        const int c = wave_tot[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    return before + inc - v;
-}
-
-// One workgroup turns counts[0 .. nb) into their exclusive prefix sums in place and hands the total on:
-//   SAMPLE   words = {n, min(k, n)}
-//   APPEND   base[0] = the cursor before this call; the cursor moves by the total, up to capacity; beyond it the overflow word is set
-enum { PC_SCAN_SAMPLE = 0, PC_SCAN_APPEND = 1 };
-
-template <int MODE>
-__global__ __launch_bounds__(PC_THREADS) void pc_scan_kernel(int nb, int32_t *__restrict__ counts, int32_t k, int32_t *__restrict__ words,
-                                                              int64_t capacity, int64_t *__restrict__ state, int64_t *__restrict__ base)
-{
-    __shared__ int wave_tot[PC_WAVES];
-    const int t = threadIdx.x;
-    int carry = 0;
-    for (int i0 = 0; i0 < nb; i0 += PC_THREADS) {
-        const int i = i0 + t;
-        const int v = i < nb ? counts[i] : 0;
-        int total;
-        const int ex = pc_block_scan(v, wave_tot, total);
-        if (i < nb) counts[i] = carry + ex;
-        carry += total;
-    }
-    if (t == 0) {
-        if (MODE == PC_SCAN_SAMPLE) {
-            words[0] = carry;
-            words[1] = carry < k ? carry : k;
-        } else {
-            const int64_t at = state[0];
-            base[0] = at;
-            const int64_t end = at + (int64_t)carry;
-            state[0] = end > capacity ? (at > capacity ? at : capacity) : end;
-            if (end > capacity) state[1] = 1;
-        }
+    const int n = dns_scan_in_place<PC_THREADS, 1>(nb, counts);
+    if (threadIdx.x == 0) {
+        words[0] = n;
+        words[1] = n < k ? n : k;
     }
 }
 
@@ -243,7 +176,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_valid_kernel(long long P, const
         const long long i = (long long)blockIdx.x * PC_SAMPLE_BLOCK + j * PC_THREADS + t;
         const bool v = i < P && pc_pixel_valid(valid, depth, i);
         int total;
-        const int rank = pc_block_rank(v, wave_tot, total);
+        const int rank = dns_block_rank<PC_THREADS>(v, wave_tot, total);
         if (WRITE && v) compact[at + rank] = (int32_t)i;
         at += total;
     }
@@ -264,14 +197,11 @@ __global__ __launch_bounds__(PC_THREADS) void pc_pick_kernel(int32_t k, uint64_t
 // ---- back-projection -----------------------------------------------------------------------------------------------------------------
 
 struct PcFrame {
-    int W, H;
-    long long P;
-    const float *depth, *rgb, *normal;
-    const uint8_t *mask;
+    DnsPixelCamera cam;
+    const float *rgb, *normal;
     const int32_t *indices, *counts;
     int32_t n_rows;
-    float fx, fy, cx, cy;
-    const float *xform, *crop;
+    const float *crop;
 };
 
 struct PcRow {
@@ -284,21 +214,14 @@ __device__ __forceinline__ PcRow pc_row(const PcFrame &f, long long j)
     PcRow o;
     o.keep = false;
     o.bad = false;
-    const long long rows = f.indices ? (f.counts ? (long long)f.counts[1] : (long long)f.n_rows) : f.P;
+    const long long rows = f.indices ? (f.counts ? (long long)f.counts[1] : (long long)f.n_rows) : f.cam.P;
     if (j >= rows || (f.indices && j >= f.n_rows)) return o;
     const long long i = f.indices ? (long long)f.indices[j] : j;
-    if (i < 0 || i >= f.P) { o.bad = true; return o; }
-    const int v = (int)(i / f.W), u = (int)(i - (long long)v * f.W);
-    const float d = (f.mask && !f.mask[i]) ? 0.f : f.depth[i];
-    // camera_utils.py:129-131: (coords - c) * depth / f, the pixel centre at + 0.5
-    const float px = __fdiv_rn(__fmul_rn(__fsub_rn((float)u + 0.5f, f.cx), d), f.fx);
-    const float py = __fdiv_rn(__fmul_rn(__fsub_rn((float)v + 0.5f, f.cy), d), f.fy);
-    const float *A = f.xform, *T = f.xform + 9, *R = f.xform + 12;
+    if (i < 0 || i >= f.cam.P) { o.bad = true; return o; }
+    dns_pixel_point(f.cam, i, dns_pixel_depth(f.cam, i), o.p);               // no gate on the depth here: the selection made it
+    const float *R = f.cam.xform + 12;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o.p[c] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(px, A[c]), __fmul_rn(py, A[3 + c])), __fmul_rn(d, A[6 + c])), T[c]);
-        o.c[c] = f.rgb[i * 3 + c];
-    }
+    for (int c = 0; c < 3; ++c) o.c[c] = f.rgb[i * 3 + c];
     if (f.normal) {
         // export_mesh.py:414-425: 2 s - 1, y and z flipped, F.normalize (x / max(|x|, 1e-12)), then the camera's rotation
         const float n0 = __fsub_rn(__fmul_rn(2.0f, f.normal[i * 3 + 0]), 1.0f);
@@ -313,16 +236,7 @@ __device__ __forceinline__ PcRow pc_row(const PcFrame &f, long long j)
     } else {
         o.n[0] = o.n[1] = o.n[2] = 0.f;
     }
-    o.keep = true;
-    if (f.crop) {
-        const float *B = f.crop, *h = f.crop + 12;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float q = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(B[4 * c], o.p[0]), __fmul_rn(B[4 * c + 1], o.p[1])), __fmul_rn(B[4 * c + 2], o.p[2])),
-                                      B[4 * c + 3]);
-            o.keep = o.keep && fabsf(q) < h[c];                              // strict on both faces; a nan coordinate is outside
-        }
-    }
+    o.keep = !f.crop || dns_in_crop_box(f.crop, o.p);
     return o;
 }
 
@@ -336,7 +250,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_backproject_kernel(PcFrame f, i
     const long long j = (long long)blockIdx.x * PC_THREADS + threadIdx.x;
     const PcRow o = pc_row(f, j);
     int total;
-    const int rank = pc_block_rank(o.keep, wave_tot, total);
+    const int rank = dns_block_rank<PC_THREADS>(o.keep, wave_tot, total);
     if (!WRITE) {
         if (threadIdx.x == 0) counts[blockIdx.x] = total;
         return;
@@ -402,8 +316,7 @@ extern "C" int dnsplat_sample_valid_pixels(int32_t width, int32_t height, const 
     const int nb = (int)pc_blocks(P, PC_SAMPLE_BLOCK);
     int32_t *block_counts = (int32_t *)scratch, *compact = block_counts + nb;
     hipLaunchKernelGGL((pc_valid_kernel<false>), dim3(nb), dim3(PC_THREADS), 0, stream, P, valid, depth, block_counts, compact);
-    hipLaunchKernelGGL((pc_scan_kernel<PC_SCAN_SAMPLE>), dim3(1), dim3(PC_THREADS), 0, stream, nb, block_counts, k, counts, (int64_t)0,
-                       (int64_t *)nullptr, (int64_t *)nullptr);
+    hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(PC_THREADS), 0, stream, nb, block_counts, k, counts);
     hipLaunchKernelGGL((pc_valid_kernel<true>), dim3(nb), dim3(PC_THREADS), 0, stream, P, valid, depth, block_counts, compact);
     if (k > 0)
         hipLaunchKernelGGL(pc_pick_kernel, dim3((unsigned)pc_blocks(k, PC_THREADS)), dim3(PC_THREADS), 0, stream, k, seed, (const int32_t *)counts,
@@ -420,12 +333,11 @@ extern "C" int dnsplat_backproject_points(const dnsplat_backproject_args *a, dns
     if (!pc_frame_ok(a->width, a->height)) return DNSPLAT_ERR_UNSUPPORTED;
     hipStream_t stream = (hipStream_t)stream_;
     PcFrame f;
-    f.W = a->width; f.H = a->height; f.P = (long long)a->width * a->height;
-    f.depth = a->depth; f.rgb = a->rgb; f.normal = a->normal; f.mask = a->mask;
+    f.cam = dns_pixel_camera(*a);
+    f.rgb = a->rgb; f.normal = a->normal;
     f.indices = a->indices; f.counts = a->indices ? a->counts : nullptr; f.n_rows = a->n_rows;
-    f.fx = a->fx; f.fy = a->fy; f.cx = a->cx; f.cy = a->cy;
-    f.xform = a->xform; f.crop = a->crop;
-    const long long rows = a->indices ? (long long)a->n_rows : f.P;
+    f.crop = a->crop;
+    const long long rows = a->indices ? (long long)a->n_rows : f.cam.P;
     if (rows == 0) return DNSPLAT_OK;
     const int nb = (int)pc_blocks(rows, PC_THREADS);
     int64_t *base = (int64_t *)a->scratch;
@@ -433,8 +345,7 @@ extern "C" int dnsplat_backproject_points(const dnsplat_backproject_args *a, dns
     float *normals = a->normal ? a->normals : nullptr;
     hipLaunchKernelGGL((pc_backproject_kernel<false>), dim3(nb), dim3(PC_THREADS), 0, stream, f, block_counts, (const int64_t *)base, a->capacity,
                        a->points, a->colors, normals, a->state);
-    hipLaunchKernelGGL((pc_scan_kernel<PC_SCAN_APPEND>), dim3(1), dim3(PC_THREADS), 0, stream, nb, block_counts, (int32_t)0, (int32_t *)nullptr,
-                       a->capacity, a->state, base);
+    hipLaunchKernelGGL(dns_append_scan_kernel<PC_THREADS>, dim3(1), dim3(PC_THREADS), 0, stream, nb, block_counts, a->capacity, a->state, base);
     hipLaunchKernelGGL((pc_backproject_kernel<true>), dim3(nb), dim3(PC_THREADS), 0, stream, f, block_counts, (const int64_t *)base, a->capacity,
                        a->points, a->colors, normals, a->state);
     DNS_CHECK_LAUNCH();

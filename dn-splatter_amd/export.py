@@ -130,6 +130,18 @@ def _crop(crop_box, device) -> Optional[Tensor]:
     return torch.cat([B[:3, :4].reshape(-1), half]).to(device).contiguous()
 
 
+def _check_append_buffers(points: Tensor, colors: Tensor, normals: Optional[Tensor], state: Tensor) -> None:
+    """What ``dnsplat_backproject_points`` and ``dnsplat_level_points`` append to: [capacity,3] buffers of one capacity, the [3] state."""
+    for name, buf in (("points", points), ("colors", colors), ("normals", normals)):
+        if buf is None:
+            continue
+        _need_gpu(buf, name)
+        if buf.dtype != torch.float32 or buf.dim() != 2 or buf.shape[1] != 3 or not buf.is_contiguous() or buf.shape[0] != points.shape[0]:
+            raise ValueError(f"{name} must be a contiguous float32 [capacity,3] buffer")
+    if state.dtype != torch.int64 or state.numel() != 3 or not state.is_cuda or not state.is_contiguous():
+        raise ValueError("state must be a contiguous int64 [3] tensor on the GPU")
+
+
 def backproject_points(depth: Tensor, rgb: Tensor, c2w_cv: Tensor, fx: float, fy: float, cx: float, cy: float, *, points: Tensor,
                        colors: Tensor, normals: Optional[Tensor] = None, state: Tensor, surface_normal: Optional[Tensor] = None,
                        mask: Optional[Tensor] = None, indices: Optional[Tensor] = None, counts: Optional[Tensor] = None, crop_box=None,
@@ -162,14 +174,7 @@ def backproject_points(depth: Tensor, rgb: Tensor, c2w_cv: Tensor, fx: float, fy
             return
     elif counts is not None:
         raise ValueError("counts without indices")
-    for name, buf in (("points", points), ("colors", colors), ("normals", normals)):
-        if buf is None:
-            continue
-        _need_gpu(buf, name)
-        if buf.dtype != torch.float32 or buf.dim() != 2 or buf.shape[1] != 3 or not buf.is_contiguous() or buf.shape[0] != points.shape[0]:
-            raise ValueError(f"{name} must be a contiguous float32 [capacity,3] buffer")
-    if state.dtype != torch.int64 or state.numel() != 3 or not state.is_cuda:
-        raise ValueError("state must be an int64 [3] tensor on the GPU")
+    _check_append_buffers(points, colors, normals, state)
     if scratch is None:
         scratch = _scratch(W, H, n_rows, dev)
     xform, crop = _xform(c2w_cv, dev), _crop(crop_box, dev)
@@ -247,7 +252,41 @@ def density_grad_normal_image(field, depth: Tensor, camera, c2w_cv: Tensor) -> T
 # ---- the exporter's loop ---------------------------------------------------------------------------------------------------------------
 
 
-class OrientedPointCloud:
+class AppendBuffers:
+    """What ``OrientedPointCloud`` and ``levelset.LevelSetCloud`` share: ``points``, ``normals`` and ``colors`` [*lead, capacity, 3] on
+    the device, their ``state`` int64 [*lead, 3] (per row: cursor, overflow, index out of range), the scratch buffer of the last frame
+    size and the read-back of a state row.  ``_ON_CPU``: what the subclass says to a device that is not the GPU."""
+
+    def __init__(self, capacity: int, device, lead: tuple = ()):
+        if capacity < 1:
+            raise ValueError(f"capacity must be positive, got {capacity}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise DnsplatError(f"{type(self).__name__} on {device}: {self._ON_CPU}")
+        self.capacity = int(capacity)
+        self.points = torch.empty(*lead, self.capacity, 3, dtype=torch.float32, device=device)
+        self.normals = torch.empty_like(self.points)
+        self.colors = torch.empty_like(self.points)
+        self.state = torch.zeros(*lead, 3, dtype=torch.int64, device=device)
+        self._scratch_key = None
+        self._scratch_buf = None
+
+    def _scratch_for(self, W: int, H: int, k: int) -> Tensor:
+        if self._scratch_key != (W, H, k):
+            self._scratch_buf = _scratch(W, H, k, self.points.device)
+            self._scratch_key = (W, H, k)
+        return self._scratch_buf
+
+    @staticmethod
+    def _cursor(row, overflow_error: str, bad_error: str) -> int:
+        """The cursor of ``row``, a state row read back to the host; raises the error its overflow or bad-index word stands for."""
+        cursor, overflow, bad = (int(v) for v in row)
+        if overflow or bad:
+            raise DnsplatError(overflow_error if overflow else bad_error)
+        return cursor
+
+
+class OrientedPointCloud(AppendBuffers):
     """Caller-sized buffers of points, normals and colours that ``add_frame`` appends to on the device.
 
         cloud = OrientedPointCloud(capacity, device)
@@ -257,26 +296,7 @@ class OrientedPointCloud:
 
     ``add_frame`` makes no host synchronisation; ``finish`` is the one place that does."""
 
-    def __init__(self, capacity: int, device):
-        if capacity < 1:
-            raise ValueError(f"capacity must be positive, got {capacity}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise DnsplatError(f"OrientedPointCloud on {device}: the point cloud is built on the GPU through libdnsplat.so (there is no CPU "
-                               "fallback; torch_export is the PyTorch restatement)")
-        self.capacity = int(capacity)
-        self.points = torch.empty(self.capacity, 3, dtype=torch.float32, device=device)
-        self.normals = torch.empty_like(self.points)
-        self.colors = torch.empty_like(self.points)
-        self.state = torch.zeros(3, dtype=torch.int64, device=device)      # cursor, overflow, index out of range
-        self._scratch_key = None
-        self._scratch_buf = None
-
-    def _scratch_for(self, W: int, H: int, k: int) -> Tensor:
-        if self._scratch_key != (W, H, k):
-            self._scratch_buf = _scratch(W, H, k, self.points.device)
-            self._scratch_key = (W, H, k)
-        return self._scratch_buf
+    _ON_CPU = "the point cloud is built on the GPU through libdnsplat.so (there is no CPU fallback; torch_export is the PyTorch restatement)"
 
     def add_frame(self, outputs, camera, *, samples_per_frame: int, filter_edges: bool = False, edge_threshold: float = 0.004,
                   edge_dilation_iterations: int = 10, mask: Optional[Tensor] = None, indices: Optional[Tensor] = None, crop_box=None,
@@ -321,11 +341,9 @@ class OrientedPointCloud:
     def finish(self) -> Tuple[Tensor, Tensor, Tensor]:
         """(points, normals, colors) trimmed to the rows appended so far.  Synchronises; raises ``DnsplatError`` if the buffers were
         too small for what the frames produced or an index lay outside its frame."""
-        cursor, overflow, bad = (int(v) for v in self.state.tolist())
-        if overflow:
-            raise DnsplatError(f"OrientedPointCloud overflow: the frames produced more than capacity = {self.capacity} points")
-        if bad:
-            raise DnsplatError("OrientedPointCloud: an index passed to add_frame lies outside its frame")
+        cursor = self._cursor(self.state.tolist(),
+                              f"OrientedPointCloud overflow: the frames produced more than capacity = {self.capacity} points",
+                              "OrientedPointCloud: an index passed to add_frame lies outside its frame")
         return self.points[:cursor], self.normals[:cursor], self.colors[:cursor]
 
 

@@ -31,7 +31,8 @@ from . import torch_levelset
 from ._lib import DnsplatError
 from ._ops import _f32c, _level_points_args, _level_rays_args, _need_gpu, _stream
 from .density import GaussianDensityField, _model_field
-from .export import MAX_PIXELS, _bytes2d, _crop, _export_c2w, _image2d, _scratch, _xform, sample_valid_pixels
+from .export import (MAX_PIXELS, AppendBuffers, _bytes2d, _check_append_buffers, _crop, _export_c2w, _image2d, _scratch, _xform,
+                     sample_valid_pixels)
 from .torch_density import KNN, SKIP
 
 RANGE_POINTS = 21           # include/dnsplat.h DNSPLAT_LEVEL_RANGE_POINTS
@@ -138,12 +139,7 @@ def level_points(field: GaussianDensityField, depth: Tensor, rgb: Tensor, camera
         raise TypeError(f"indices must be a contiguous 1-D int32 tensor, got {indices.dtype} {tuple(indices.shape)}")
     if indices.numel() == 0:
         return
-    for name, buf in (("points", points), ("colors", colors), ("normals", normals)):
-        _need_gpu(buf, name)
-        if buf.dtype != torch.float32 or buf.dim() != 2 or buf.shape[1] != 3 or not buf.is_contiguous() or buf.shape[0] != points.shape[0]:
-            raise ValueError(f"{name} must be a contiguous float32 [capacity,3] buffer")
-    if state.dtype != torch.int64 or state.numel() != 3 or not state.is_cuda or not state.is_contiguous():
-        raise ValueError("state must be a contiguous int64 [3] tensor on the GPU")
+    _check_append_buffers(points, colors, normals, state)
     if t_hit.dtype != torch.float32 or t_hit.numel() != H * W or not t_hit.is_contiguous() or closest.dtype != torch.int32 or closest.numel() != H * W:
         raise ValueError("t_hit (float32) and closest (int32) must be the [P] rows of level_rays")
     if scratch is None:
@@ -154,7 +150,7 @@ def level_points(field: GaussianDensityField, depth: Tensor, rgb: Tensor, camera
     _lib.run("dnsplat_level_points", L.dnsplat_level_points, a, _stream())
 
 
-class LevelSetCloud:
+class LevelSetCloud(AppendBuffers):
     """One caller-sized buffer of points, normals and colours per surface level that ``add_frame`` appends to on the device.
 
         cloud = LevelSetCloud((0.1, 0.3, 0.5), capacity, device)
@@ -164,28 +160,11 @@ class LevelSetCloud:
 
     ``add_frame`` makes no host synchronisation; ``finish`` is the one place that does."""
 
+    _ON_CPU = "the cloud is built on the GPU through libdnsplat.so (torch_levelset is the PyTorch restatement)"
+
     def __init__(self, surface_levels: Sequence[float], capacity: int, device):
         self.levels = _levels(surface_levels)
-        if capacity < 1:
-            raise ValueError(f"capacity must be positive, got {capacity}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise DnsplatError(f"LevelSetCloud on {device}: the cloud is built on the GPU through libdnsplat.so (torch_levelset is the "
-                               "PyTorch restatement)")
-        self.capacity = int(capacity)
-        nl = len(self.levels)
-        self.points = torch.empty(nl, self.capacity, 3, dtype=torch.float32, device=device)
-        self.normals = torch.empty_like(self.points)
-        self.colors = torch.empty_like(self.points)
-        self.state = torch.zeros(nl, 3, dtype=torch.int64, device=device)      # per level: cursor, overflow, index out of range
-        self._scratch_key = None
-        self._scratch_buf = None
-
-    def _scratch_for(self, W: int, H: int, k: int) -> Tensor:
-        if self._scratch_key != (W, H, k):
-            self._scratch_buf = _scratch(W, H, k, self.points.device)
-            self._scratch_key = (W, H, k)
-        return self._scratch_buf
+        super().__init__(capacity, device, lead=(len(self.levels),))      # one row of buffers and one state row per level
 
     def add_frame(self, field: GaussianDensityField, outputs, camera, *, num_samples: int, normals: Optional[Tensor] = None,
                   mask: Optional[Tensor] = None, return_normal: str = "closest_gaussian", seed: int = 0, crop_box=None,
@@ -215,11 +194,9 @@ class LevelSetCloud:
         """{level: {"points", "normals", "colors"}} trimmed to the rows appended so far.  Synchronises; raises ``DnsplatError`` if a
         buffer was too small for what the frames produced."""
         result = {}
-        for l, (level, (cursor, overflow, bad)) in enumerate(zip(self.levels, self.state.tolist())):
-            if overflow:
-                raise DnsplatError(f"LevelSetCloud overflow: level {level} produced more than capacity = {self.capacity} points")
-            if bad:
-                raise DnsplatError("LevelSetCloud: an index lies outside its frame")
+        for l, (level, row) in enumerate(zip(self.levels, self.state.tolist())):
+            cursor = self._cursor(row, f"LevelSetCloud overflow: level {level} produced more than capacity = {self.capacity} points",
+                                  "LevelSetCloud: an index lies outside its frame")
             result[level] = {"points": self.points[l, :cursor], "normals": self.normals[l, :cursor], "colors": self.colors[l, :cursor]}
         return result
 

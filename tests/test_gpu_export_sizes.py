@@ -31,7 +31,7 @@ DF_THREADS = 256                # density_common.h: points per workgroup of the 
 DF_SCAN_THREADS = 1024          # df_scan_kernel: one workgroup ...
 DF_SCAN_PER = 4                 # ... of 4 entries per thread: 4096 cell counts per trip
 DF_MINMAX_BLOCKS = 256          # the cap of df_minmax_kernel's grid
-PC_THREADS = 256                # pointcloud.hip: rows per workgroup of the appends, block counts per trip of pc_scan_kernel
+PC_THREADS = 256                # pointcloud.hip: rows per workgroup of the appends, block counts per trip of the one-workgroup scans
 PC_SAMPLE_PER = 4               # pixels per thread of the sampler's count kernel: 1024 pixels per block count
 MC_THREADS = 256                # marching.hip: threads of mc_scan_bases
 MC_SCAN_WORDS = 1024            # words of 64 lattice points per scan block
@@ -219,7 +219,7 @@ def test_sampler_past_256_block_counts(export, H, W):
     P = H * W
     nb = _ceil(P, PC_SAMPLE_BLOCK)
     if H == 512:
-        assert nb == PC_THREADS and P % PC_SAMPLE_BLOCK == 0                 # the control: one trip of pc_scan_kernel<SAMPLE>
+        assert nb == PC_THREADS and P % PC_SAMPLE_BLOCK == 0                 # the control: one trip of pc_scan_kernel
     else:
         assert nb == PC_THREADS + 1 and P % PC_SAMPLE_BLOCK == PC_SAMPLE_BLOCK // 2      # a second trip of one, half full block
     valid = _validity(H, W)
@@ -293,7 +293,7 @@ def test_backprojection_of_all_pixels_past_256_row_blocks(export, te, H, W):
     count, kept rows in order, points and normals within their bounds, colours bit for bit, nothing behind the cursor."""
     P = H * W
     nb = _ceil(P, PC_THREADS)
-    assert nb == (PC_THREADS if H == 256 else PC_THREADS + 1)                # one trip of pc_scan_kernel<APPEND>, or a second of one block
+    assert nb == (PC_THREADS if H == 256 else PC_THREADS + 1)                # one trip of dns_append_scan_kernel, or a second of one block
     case = _bp_case(te, H, W)
     f, inside = case["f"], case["inside"]
     guard = 8
@@ -380,7 +380,7 @@ def _level_points(c, l, indices, mode, box, bufs, state):
 @pytest.mark.parametrize("order", ["raster", "spread"])
 @pytest.mark.parametrize("mode", ["closest_gaussian", "analytical"])
 def test_level_points_past_256_row_blocks(level_case, te, mode, order):
-    """dnsplat_level_points over all 65 792 pixels in one call (257 row blocks: two trips of ls_scan_kernel) equals, row for row and bit
+    """dnsplat_level_points over all 65 792 pixels in one call (257 row blocks: two trips of dns_append_scan_kernel) equals, row for row and bit
     for bit, the same rows appended in two calls of at most 65 536 — the one-trip path test_gpu_levelset.py holds to the fp64
     restatement.  Independently: the count is the number of listed pixels with a hit (inside the box, where there is one), and
     without a box the colours are those pixels' in list order.
