@@ -596,9 +596,12 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) void project_fwd_kernel(FwdParams
     const int tw = (p.c.width + p.c.tile_size - 1) / p.c.tile_size;
     const int th = (p.c.height + p.c.tile_size - 1) / p.c.tile_size;
     if (p.c.antialiased) opac *= st.compensation;
-    // alpha = min(0.999, opacity x vis) can only clamp for a splat whose opacity exceeds the cap (vis <= 1): tell the compositing
-    // backward whether this frame holds one at all (dnsplat_proj_out.saturation_flag; many lanes may store the same 1)
-    if (p.o.saturation_flag && opac > (float)DNS_ALPHA_MAX) *p.o.saturation_flag = 1u;
+    // alpha = min(0.999, opacity x vis) can only clamp for a splat whose opacity exceeds the cap (vis <= 1), and the exponent of a
+    // pair can only round to a positive number for a conic that is not definite with a margin (dns_conic_benign): tell the
+    // compositing kernels whether this frame holds such a visible Gaussian at all, i.e. whether they need their careful loops
+    // (dnsplat_proj_out.saturation_flag; many lanes may store the same 1)
+    if (p.o.saturation_flag && (opac > (float)DNS_ALPHA_MAX || !dns_conic_benign(st.conic[0], st.conic[1], st.conic[2])))
+        *p.o.saturation_flag = 1u;
     int x0, y0, x1, y1;
     dns_tile_bbox(st.mean2d[0], st.mean2d[1], st.radius, p.c.tile_size, tw, th, x0, y0, x1, y1);
     const int tiles_ref = (y1 - y0) * (x1 - x0);          // gsplat's count (A.3): what info["tiles_per_gauss"] / num_tiles_hit report

@@ -167,9 +167,11 @@ __device__ __forceinline__ f2 pk_mul_bcast(f2 a, f2 b, int hi)
 // MASKS: which list entries can contribute to this half tile comes from the forward (a.keep_masks) instead of being re-derived
 // with dns_cull_rect: same decisions (the forward ran the same test on the same records), no record gathers for rejected
 // entries, and the test's registers (the kernel's VGPR peak) are gone.
-// CLAMP_LOOP = false: the step loop without the alpha cap (no min, no "gradient only where not clamped" compare and select: 82 instead
-// of 86 vector instructions per step, -3.6 % measured).  Only right when no splat of the launch has an opacity above the cap, which
-// the projection reports in a device word (dnsplat_proj_out.saturation_flag).  Nothing on the host knows the answer without a
+// CLAMP_LOOP = false: the step loop without the per-pair tests a well-conditioned frame cannot fail — no alpha cap (no min, no
+// "gradient only where not clamped" compare and select: 82 instead of 86 vector instructions per step, -3.6 % measured) and no
+// `e <= 0` (two v_cmp: 65 instead of 67, -1.8 % paired; profiles/ab_benign_fast_paths.txt).  Only right when no visible splat of the
+// launch has an opacity above the cap or a conic that fails dns_conic_benign (splat_common.h), which the projection reports in a
+// device word (dnsplat_proj_out.saturation_flag).  Nothing on the host knows the answer without a
 // sync, so both instantiations are launched and the one that does not apply leaves at its first instruction (a few us).
 // DET: deterministic gradient scatter (DNSPLAT_DETERMINISTIC, a test / debug mode).  The sums of a (half tile, splat) are the same
 // numbers in every run — they are formed in registers in stream order — but the order in which the atomic rows of the ~14 tiles x 2
@@ -530,10 +532,11 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
             // otherwise hipcc's wait insertion may find one of their registers overwritten in the loop and put an
             // s_waitcnt lgkmcnt(0) right behind the row loads of every step (tools/check_asm_hazards.py: "early wait").
             __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0), vmcnt / expcnt untouched
-            // The step loop, with or without the alpha cap (CLAMP_LOOP).  alpha = min(0.999, opacity x vis) can only clamp for a splat
+            // The step loop, careful or fast (CLAMP_LOOP).  alpha = min(0.999, opacity x vis) can only clamp for a splat
             // whose opacity exceeds 0.999 (vis <= 1 for a valid pair); while the launch holds no such splat — random initialisation,
             // most of training — the clamp, the "gradient only where not clamped" compare and one of the two selects per
-            // splat drop out of the step (alpha and its gradient weight are then the same number).
+            // splat drop out of the step (alpha and its gradient weight are then the same number).  The same word of the projection
+            // says that every visible conic is definite with a margin, and then the exponent's sign test drops out as well.
             auto step_loop = [&](auto clamp_tag) {
             constexpr bool CLAMP = decltype(clamp_tag)::value;
             for (int s = 0; s < nsteps; ++s) {
@@ -562,8 +565,10 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
                 float SA = cst.x, SB = cst.z;
                 const int bin_final = __float_as_int(cst.w);
                 // an idle slot has read the dummy row's bin_final = -1, below every list index
-                const bool valid_a = cmp_a <= bin_final && e.x <= 0.f && al_a >= (float)DNS_ALPHA_MIN;
-                const bool valid_b = cmp_b <= bin_final && e.y <= 0.f && al_b >= (float)DNS_ALPHA_MIN;
+                // the careful loop skips a pair whose exponent rounded to a positive number; the fast one runs only in frames whose
+                // conics cannot produce one (dns_conic_benign).  A NaN exponent fails the alpha test in both.
+                const bool valid_a = cmp_a <= bin_final && (!CLAMP || e.x <= 0.f) && al_a >= (float)DNS_ALPHA_MIN;
+                const bool valid_b = cmp_b <= bin_final && (!CLAMP || e.y <= 0.f) && al_b >= (float)DNS_ALPHA_MIN;
                 if (COUNT) n_pairs += __popcll(dns_ballot(valid_a)) + __popcll(dns_ballot(valid_b));
                 {   // straight-line: an idle step costs the same as a busy one, but no phi copies at a join
                     // an invalid pair takes alpha = 0 (=> 1/(1-alpha) = 1, weight 0: state and sums unchanged) and m = 0

@@ -130,7 +130,13 @@ __device__ __forceinline__ float sel0(uint64_t mask, float a)
 // evaluated and pairs blended into a.counters (bench.py's VALU roofline); never the instantiation that is timed.
 // (A clamp-free twin as in raster_bwd.hip was measured here too: the two `min` it drops from 43 vector instructions per splat
 // bought nothing — 0.562 vs 0.561 ms — and its differently scheduled code broke the bit-identity of the raw composite between
-// the instantiations, which tests/test_reference_golden.py relies on.  Removed.)
+// the instantiations, which tests/test_reference_golden.py relies on.  Removed.
+// Tried once more with the backward's wider condition — a second body of the per-splat loop without the two `min` AND without the
+// two `e <= 0` ballots, chosen per 64-entry batch by a ballot over the staged records (opacity within the cap and
+// dns_conic_benign); the forward call carries no flag word.  hipcc's SLP pass packs the second body differently (the exponent as
+// scalar FMAs, the odd channel as a pair): 45 instead of 46 vector and 21 instead of 23 scalar instructions in the loop, the hand-placed
+// exit unchanged, but two accumulator layouts live across the batch loop, 82 VGPRs instead of 66.  0.4549 vs 0.4548 ms in paired
+// replays (docs/history.md, section 22).  Not kept: this loop does not get faster by dropping instructions.)
 template <int D, bool DN, bool COUNT = false>
 __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kernel(FwdArgs a)
 {

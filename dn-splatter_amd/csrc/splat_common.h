@@ -139,6 +139,34 @@ __device__ __forceinline__ float dns_exponent(const DnsConicE &q, float dx, floa
     return __builtin_fmaf(dx, u, dy * w);
 }
 
+// WHEN THE TEST `e <= 0` CANNOT FAIL.  dns_exponent() rounds six times:
+//     p1 = fl(na dx)   u = fl(nb dy + p1)   p2 = fl(nb dx)   w = fl(nc dy + p2)   p3 = fl(dy w)   e = fl(dx u + p3)
+// with fl(x) = x (1 + d), |d| <= eps = 2^-24 while nothing under- or overflows.  Multiplying out, every one of the four terms
+// na dx^2, nb dx dy (twice), nc dy^2 of the exact form reaches e through at most three roundings, so
+//     e = E + r,    E = na dx^2 + 2 nb dx dy + nc dy^2  (exact, of the STORED na, nb, nc),    |r| <= ((1 + eps)^3 - 1) S,
+//     S = |na| dx^2 + 2 |nb| |dx dy| + |nc| dy^2   (the sum of the terms' magnitudes).
+// With na, nc < 0 and rho = |nb| / sqrt(na nc):  m = |na| dx^2 + |nc| dy^2 >= 2 sqrt(na nc) |dx dy| (AM-GM), so the cross term
+// t = 2 |nb dx dy| <= rho m, and  -E >= m - t >= (1 - rho) m,  S = m + t <= (1 + rho) m:
+//     S <= (1 + rho) / (1 - rho) |E|,        e <= 0 is certain once   3.0000002 eps (1 + rho) / (1 - rho) < 1.
+// The rule below is stated on the record's conic (a, b, c) as stored: b^2 <= (1 - 2^-12) a c.  Its own three roundings and the
+// three of dns_conic_e() (na = fl(k a), ...) move rho^2 by a factor within (1 + eps)^7: rho^2 <= 1 - 2^-12 + 2^-21, hence
+// 1 - rho >= (1 - rho^2) / 2 >= 2^-13.001, (1 + rho) / (1 - rho) <= 2^14.001 = 1.64e4 and 3 eps S / |E| <= 2.93e-3: a margin of
+// 340x.  (The largest constant with the 16x margin asked of such a bound would be 1 - 2^-16; nothing needs it.)
+// "Nothing under- or overflows": a, c in [2^-40, 2^40] — eight orders of magnitude beyond what a projection with eps2d > 0 and a
+// radius clip can produce.  Then a c and b^2 are finite and normal (inf <= inf cannot pass), and for a pixel offset that is 0 or at
+// least 2^-25 in magnitude (a difference of a mean and a pixel centre k + 1/2 cannot be smaller) and at most 2^14, every product
+// above lies between 2^-116 and 2^69 or is an exact zero, and |E| >= 2^-13 2^-41 2^-50 is far above the subnormals.
+// dx = dy = 0 gives e = +0, which passes `<= 0` as it always did.  A NaN in a, b or c fails a comparison: not benign.
+// tests/test_conic_benign_bound.py restates the sequence in numpy and checks 10^7 pairs, a subset in exact rationals.
+// Evaluated by the projection (which raises dnsplat_proj_out.saturation_flag for a visible Gaussian that fails it) on the record
+// floats as they are stored; contraction is pinned off so that the products round before they are compared.
+__device__ __forceinline__ bool dns_conic_benign(float a, float b, float c)
+{
+#pragma clang fp contract(off)
+    const float lo = 0x1p-40f, hi = 0x1p40f;
+    return a >= lo && a <= hi && c >= lo && c <= hi && b * b <= (1.f - 0x1p-12f) * (a * c);
+}
+
 __device__ __forceinline__ float dns_exp2(float e) { return __builtin_amdgcn_exp2f(e); }
 
 // Conservative test "no pixel centre of the rectangle [xl,xh] x [yl,yh] can pass alpha >= 1/255 for this

@@ -136,9 +136,12 @@ typedef struct dnsplat_proj_out {
     float *normals_world;      /* [N,3] or NULL: what dn_model.py:558 stores into gauss_params["normals"] */
     int32_t with_depth_channel;   /* append camera-space depth as a channel (RGB+D / RGB+ED) */
     int32_t with_normal_channels; /* append the 3 camera-frame normal channels (needs camera.normal_frame) */
-    uint32_t *saturation_flag;    /* NULL, or a device word the caller zeroed: set to 1 when a visible Gaussian's opacity (after
-                                     the antialiasing compensation) exceeds 0.999, i.e. when alpha = min(0.999, o x vis) can clamp
-                                     at all in this frame (A.5).  dnsplat_raster_args.saturation_flag takes it. */
+    uint32_t *saturation_flag;    /* NULL, or a device word the caller zeroed; nonzero afterwards = "the careful compositing loops are
+                                     required": set to 1 when a visible Gaussian's opacity (after the antialiasing compensation)
+                                     exceeds 0.999, i.e. when alpha = min(0.999, o x vis) can clamp at all in this frame (A.5), or
+                                     when a visible Gaussian's conic is not positive definite with a margin (b^2 <= (1 - 2^-12) a c,
+                                     a, c in [2^-40, 2^40]), i.e. when a pair's exponent could round to a positive number.  Culled
+                                     Gaussians never raise it.  dnsplat_raster_args.saturation_flag takes it. */
     int32_t *tiles_bin;           /* required iff camera.tight_tiles: [N] tile count over the TIGHT box (what dnsplat_bin_args.tiles_per_gauss
                                      must then be given); tiles_per_gauss itself always receives gsplat's count (A.3), which is what
                                      info["tiles_per_gauss"] / DNSplatterModel.num_tiles_hit (dn_model.py:524) report */
@@ -278,8 +281,10 @@ typedef struct dnsplat_raster_args {
                                                     [2] live (pixel, splat) pairs evaluated  [3] pairs blended
                                            backward [4] (pixel, splat) slots issued (steps x 128)  [5] pairs replayed */
     const uint32_t *saturation_flag;    /* NULL, or dnsplat_proj_out.saturation_flag of the projection(s) behind `splats`: if the word
-                                           is 0 no pair of this launch can clamp and dnsplat_raster_bwd (only; the forward ignores it) runs its step loop without
-                                           the clamp handling (same results, ~3.6 % fewer cycles); read on the device, no host sync */
+                                           is 0 no pair of this launch can clamp or have a positive exponent, and dnsplat_raster_bwd (only; the
+                                           forward ignores it) runs its step loop without the clamp handling and without the exponent's
+                                           sign test (same results, ~5 % fewer cycles); read on the device, no host sync.  A caller who
+                                           writes records by hand passes a nonzero word (or NULL) unless they satisfy both conditions */
     const int32_t *tile_ends;           /* NULL: tile t's list is [tile_offsets[t], tile_offsets[t+1]).  Else dnsplat_bin_args.tile_ends:
                                            the list is [tile_offsets[t], tile_ends[t]) and empty where tile_ends[t] <= tile_offsets[t] */
     void *zero_fill;                    /* dnsplat_raster_fwd only: NULL, or a device buffer of zero_fill_bytes (multiple of 16) the launch clears

@@ -12,6 +12,7 @@ for v in "$@" "$1"; do
 import json,sys
 d=json.loads(sys.stdin.read())
 st=d['stages']
-print('$v |', d['value'], 'fps', d['ms_per_step'], 'ms | ' + ' '.join('%s %.4f' % (k.replace('dnsplat_',''), v['ms']) for k, v in st.items()))" || exit 1
+print('$v |', d['value'], 'fps', d['ms_per_step'], 'ms | ' + ' '.join('%s %.4f' % (k.replace('dnsplat_',''), v['ms']) for k, v in st.items())
+      + ' | careful loops %s' % d['config'].get('alpha_clamp_twin_active'))" || exit 1
   done
 done
