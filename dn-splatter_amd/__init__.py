@@ -32,6 +32,9 @@ from . import levelset, torch_levelset  # noqa: F401
 from .levelset import LevelSetCloud, export_level_set_points, install_level_sets, level_surface_points  # noqa: F401
 from . import marching, torch_marching  # noqa: F401
 from .marching import marching_cubes, marching_cubes_mesh, mcubes_marching_cubes  # noqa: F401
+from . import geometry, torch_geometry  # noqa: F401
+from .geometry import (PDMetrics, calculate_accuracy, calculate_completeness, cloud_distances, cloud_metrics, install_pd_metrics,  # noqa: F401
+                       mesh_metrics, sample_mesh_surface)
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -42,5 +45,7 @@ __all__ = [
     "export_oriented_points", "density", "torch_density", "GaussianDensityField", "build_index", "density_volume", "install_density", "knn",
     "levelset", "torch_levelset", "LevelSetCloud", "export_level_set_points", "install_level_sets", "level_surface_points",
     "marching", "torch_marching", "marching_cubes", "marching_cubes_mesh", "mcubes_marching_cubes",
+    "geometry", "torch_geometry", "PDMetrics", "calculate_accuracy", "calculate_completeness", "cloud_distances", "cloud_metrics",
+    "install_pd_metrics", "mesh_metrics", "sample_mesh_surface",
     "build_library", "load_library", "DnsplatError",
 ]

@@ -201,6 +201,22 @@ class McArgs(ctypes.Structure):
     ]
 
 
+class CloudDistancesArgs(ctypes.Structure):
+    _fields_ = [
+        ("N", c_int32), ("index", c_void_p), ("M", c_int64), ("src", c_void_p), ("src_normals", c_void_p), ("tgt_normals", c_void_p),
+        ("threshold", ctypes.c_double), ("percentile", ctypes.c_double),
+        ("dist2", c_void_p), ("idx", c_void_p), ("absdot", c_void_p), ("scalars", c_void_p), ("counts", c_void_p), ("scratch", c_void_p),
+    ]
+
+
+class MeshSampleArgs(ctypes.Structure):
+    _fields_ = [
+        ("S", c_int64), ("seed", ctypes.c_uint64), ("V", c_int32), ("T", c_int32),
+        ("cdf", c_void_p), ("vertices", c_void_p), ("triangles", c_void_p), ("face_normals", c_void_p),
+        ("points", c_void_p), ("normals", c_void_p), ("faces", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -229,6 +245,8 @@ EXPORTS = [
     "dnsplat_level_rays", "dnsplat_level_points",
     # likewise: marching cubes on a lattice
     "dnsplat_mc_scratch_bytes", "dnsplat_mc_count", "dnsplat_mc_emit",
+    # likewise: the geometry scores (cloud distances, mesh areas and samples)
+    "dnsplat_cloud_distances_scratch_bytes", "dnsplat_cloud_distances", "dnsplat_mesh_areas", "dnsplat_mesh_sample",
 ]
 
 _lib = None
@@ -332,11 +350,16 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_mc_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
         L.dnsplat_mc_count.argtypes = [ctypes.POINTER(McArgs), c_void_p]
         L.dnsplat_mc_emit.argtypes = [ctypes.POINTER(McArgs), c_void_p]
+        L.dnsplat_cloud_distances_scratch_bytes.restype = c_size_t
+        L.dnsplat_cloud_distances_scratch_bytes.argtypes = [c_int64]
+        L.dnsplat_cloud_distances.argtypes = [ctypes.POINTER(CloudDistancesArgs), c_void_p]
+        L.dnsplat_mesh_areas.argtypes = [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.dnsplat_mesh_sample.argtypes = [ctypes.POINTER(MeshSampleArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
                             "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
-                            "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes"):
+                            "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

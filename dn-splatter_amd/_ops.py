@@ -12,7 +12,7 @@ dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rast
 get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
 
 One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
-``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``, ``_mc_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
+``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``, ``_mc_args``, ``_cloud_distances_args``, ``_mesh_sample_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, MeshSampleArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -424,6 +424,26 @@ def _mc_args(volume, level, scratch, counts, vertices=None, triangles=None, cap_
     a.counts = _ptr(counts)
     a.cap_v, a.cap_t = cap_v, cap_t
     a.vertices, a.triangles, a.status = _ptr(vertices), _ptr(triangles), _ptr(status)
+    return a
+
+
+def _cloud_distances_args(N, index, src, src_normals, tgt_normals, threshold, percentile, dist2, idx, absdot, scalars, counts, scratch):
+    a = CloudDistancesArgs()
+    a.N, a.index = N, _ptr(index)
+    a.M, a.src = src.shape[0], _ptr(src)
+    a.src_normals, a.tgt_normals = _ptr(src_normals), _ptr(tgt_normals)
+    a.threshold, a.percentile = threshold, percentile
+    a.dist2, a.idx, a.absdot = _ptr(dist2), _ptr(idx), _ptr(absdot)
+    a.scalars, a.counts, a.scratch = _ptr(scalars), _ptr(counts), _ptr(scratch)
+    return a
+
+
+def _mesh_sample_args(seed, cdf, vertices, triangles, face_normals, points, normals, faces):
+    a = MeshSampleArgs()
+    a.S, a.seed = points.shape[0], seed
+    a.V, a.T = vertices.shape[0], triangles.shape[0]
+    a.cdf, a.vertices, a.triangles, a.face_normals = _ptr(cdf), _ptr(vertices), _ptr(triangles), _ptr(face_normals)
+    a.points, a.normals, a.faces = _ptr(points), _ptr(normals), _ptr(faces)
     return a
 
 

@@ -60,7 +60,9 @@ extern "C" {
  * dnsplat_eval_metrics_scratch_bytes: the evaluation scores; dnsplat_knn_grid_dim / dnsplat_knn_index_bytes / dnsplat_knn_build /
  * dnsplat_knn_query / dnsplat_density_pack / dnsplat_density_eval / dnsplat_density_args: the Gaussian density field;
  * dnsplat_level_rays / dnsplat_level_points / dnsplat_level_rays_args / dnsplat_level_points_args: the level-set surface points;
- * dnsplat_mc_scratch_bytes / dnsplat_mc_count / dnsplat_mc_emit / dnsplat_mc_args: marching cubes on a lattice). */
+ * dnsplat_mc_scratch_bytes / dnsplat_mc_count / dnsplat_mc_emit / dnsplat_mc_args: marching cubes on a lattice;
+ * dnsplat_cloud_distances / dnsplat_cloud_distances_scratch_bytes / dnsplat_cloud_distances_args / dnsplat_mesh_areas /
+ * dnsplat_mesh_sample / dnsplat_mesh_sample_args: the geometry scores). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -875,6 +877,109 @@ typedef struct dnsplat_mc_args {
 size_t dnsplat_mc_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);   /* 0 for an invalid size */
 int dnsplat_mc_count(const dnsplat_mc_args *args, dnsplat_stream_t stream);
 int dnsplat_mc_emit(const dnsplat_mc_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ geometry scores (added after ABI 15, found by symbol)
+ * The reference's point-cloud and mesh scores: PDMetrics / calculate_accuracy / calculate_completeness (metrics.py:11-56) and
+ * compute_metrics with distance_p2p and get_threshold_percentage (eval/eval_mesh_vis_cull.py:290-397, the same function in
+ * eval_mesh_mushroom_vis_cull.py:25-142), where the reference builds a scipy cKDTree on the CPU per direction and samples the meshes
+ * with trimesh.  Everything is caller-allocated; nothing is read on the host, allocated or synchronised; no floating-point atomic:
+ * equal inputs give equal bits.
+ *
+ * dnsplat_cloud_distances — ONE direction of distance_p2p with every scalar the callers take from it.  Per source point m of M, one
+ *   thread:
+ *   nearest    the target of lowest (d2, index) among the N points `index` was built over (dnsplat_knn_build), d2 as dnsplat_knn_query
+ *              forms it, in DOUBLE: fma(dz, dz, fma(dy, dy, dx dx)).  A tie goes to the lowest index (scipy leaves ties unspecified).
+ *   absdot     with both normal arrays: | n_src / |n_src| . n_tgt[idx] / |n_tgt[idx]| | in double, |n| = sqrt((x x + y y) + z z), the dot
+ *              (a + b) + c, plain IEEE without contraction: a zero normal gives nan, as in the reference.
+ *   outputs    dist2 [M] double (required: the selection reads it back), idx [M] int32 or NULL, absdot [M] double or NULL.
+ *   non-finite a source point with a nan or inf coordinate reads nothing: idx = -1, dist2 = absdot = nan; it counts in N_NONFINITE and
+ *              makes the means, the percentile, min and max nan (numpy's behaviour on a nan distance).  The same holds for a point
+ *              that no target can be compared with (every target has a nan coordinate).
+ *   scalars    device double [DNSPLAT_GEOM_COUNT] at the DNSPLAT_GEOM_* indices: the means of d = sqrt(d2), of d2 and of absdot (nan
+ *              without normals), the percentile, the shares d < threshold (calculate_completeness) and d <= threshold
+ *              (get_threshold_percentage: precision and recall), min d, max d, and the two order statistics of d2 the percentile was
+ *              interpolated from.  The unused tail is 0.
+ *   counts     device int64 [DNSPLAT_GEOM_COUNTS]: n = M, the two threshold counts, the non-finite rows.
+ *   percentile numpy's default method (`linear`) on d: h = (n - 1) (q / 100) in double, the order statistics of rank floor(h) and
+ *              min(floor(h) + 1, n - 1) found EXACTLY by a radix selection on the 64-bit patterns of d2 (non-negative doubles order as
+ *              their patterns, so the order of d2 is the order of d) in six integer histogram rounds (11 + 11 + 11 + 11 + 10 + 10 bits)
+ *              for both ranks at once; then a = sqrt(lo), b = sqrt(hi), g = h - floor(h) and numpy's _lerp: g >= 0.5 ? b - (b - a) (1 - g)
+ *              : a + (b - a) g, in double.  h depends on M and q alone: the ranks are arguments of the kernels.
+ *   sums       one partial per workgroup of 256 points (sums in double, counts as integers), folded in a fixed order.
+ *   scratch    dnsplat_cloud_distances_scratch_bytes(M) bytes (a host function; 0 for M outside 1 .. 2^31 - 1), 8-byte aligned.  No
+ *              precondition on its contents, and they need not survive.
+ *   One memset and thirteen launches.  Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL args / index / src / dist2 / scalars /
+ *   counts / scratch, M < 1, N < 1, half a normal pair, a percentile outside [0, 100] (a nan included); DNSPLAT_ERR_UNSUPPORTED for
+ *   M > 2^31 - 1 (N is an int32).
+ *
+ * dnsplat_mesh_areas — per triangle of `triangles` [T,3] int32 over `vertices` [V,3] fp32: area = |cross(v1 - v0, v2 - v0)| / 2 in double
+ *   from the exactly converted vertices, and the unit face normal cross / |cross| rounded to fp32 [T,3].  A zero-area face gets normal 0;
+ *   a triangle with an index outside [0, V), or with a non-finite cross product, gets area 0 and normal 0 and reads nothing out of
+ *   bounds.  One launch.  The inclusive prefix sum of the areas is the caller's (any double scan; the Python layer uses torch.cumsum).
+ *
+ * dnsplat_mesh_sample — mesh.sample(count, return_index=True) as a canonical function of (mesh, cdf, seed).  Sample i of S, one thread:
+ *   words      mix(x) = pc_mix32 of the pixel sampler (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16).
+ *              key = mix((uint32)seed ^ mix((uint32)(seed >> 32) + 0x9e3779b9)); c = mix((uint32)i ^ key);
+ *              w_k = mix(c + (k + 1) 0x9e3779b9), k = 0, 1, 2 (uint32 arithmetic): a counter-based integer hash, no state.
+ *   face       t = ((double)w_0 + 0.5) / 2^32 * cdf[T - 1]; f = the first index with cdf[f] > t (binary search).  A face whose cdf entry
+ *              equals its predecessor's (area 0) can therefore never be drawn.
+ *   point      u = w_1 >> 8, v = w_2 >> 8; if u + v > 2^24 both are reflected to 2^24 - u, 2^24 - v; r1 = u / 2^24, r2 = v / 2^24 (exact
+ *              in fp32); p = (v0 + r1 (v1 - v0)) + r2 (v2 - v0) in fp32 in that order, no contraction.
+ *   outputs    points [S,3] fp32, normals [S,3] fp32 (a copy of face_normals[f]), faces [S] int32.
+ *   A cdf whose last entry is not a positive finite number (no face can be drawn) gives points nan, normals 0, faces -1.  Whatever cdf is
+ *   given, the vertex indices of the drawn face are tested against V before anything is read through them (point nan, normal 0, the
+ *   face index kept).  One launch.  PARITY UNPINNED against trimesh, whose draws come from numpy's global generator.
+ *   Returns without a launch: DNSPLAT_ERR_INVALID_ARG for NULL args / cdf / vertices / triangles / face_normals (/ an output with S > 0),
+ *   S < 0, V < 1, T < 1; DNSPLAT_ERR_UNSUPPORTED for S > 2^31 - 1.  S == 0 returns 0. */
+#define DNSPLAT_GEOM_MEAN_D 0          /* mean of d */
+#define DNSPLAT_GEOM_MEAN_D2 1         /* mean of d^2 */
+#define DNSPLAT_GEOM_MEAN_ABSDOT 2     /* mean of |n_src . n_tgt|; nan without normals */
+#define DNSPLAT_GEOM_PERCENTILE 3      /* numpy.percentile(d, percentile) */
+#define DNSPLAT_GEOM_SHARE_LT 4        /* share with d < threshold */
+#define DNSPLAT_GEOM_SHARE_LE 5        /* share with d <= threshold */
+#define DNSPLAT_GEOM_MIN_D 6
+#define DNSPLAT_GEOM_MAX_D 7
+#define DNSPLAT_GEOM_ORDER_LO_D2 8     /* d^2 of rank floor(h) */
+#define DNSPLAT_GEOM_ORDER_HI_D2 9     /* d^2 of rank min(floor(h) + 1, n - 1) */
+#define DNSPLAT_GEOM_COUNT 12
+#define DNSPLAT_GEOM_N 0
+#define DNSPLAT_GEOM_N_LT 1
+#define DNSPLAT_GEOM_N_LE 2
+#define DNSPLAT_GEOM_N_NONFINITE 3
+#define DNSPLAT_GEOM_COUNTS 4
+typedef struct dnsplat_cloud_distances_args {
+    int32_t N;                  /* points the index was built over */
+    const void *index;          /* dnsplat_knn_build's, over the TARGET points */
+    int64_t M;                  /* source points */
+    const float *src;           /* [M,3] */
+    const float *src_normals;   /* [M,3] or NULL */
+    const float *tgt_normals;   /* [N,3] or NULL; both or neither */
+    double threshold;
+    double percentile;          /* in [0, 100] */
+    double *dist2;              /* [M] */
+    int32_t *idx;               /* [M] or NULL */
+    double *absdot;             /* [M] or NULL */
+    double *scalars;            /* device [DNSPLAT_GEOM_COUNT] */
+    int64_t *counts;            /* device [DNSPLAT_GEOM_COUNTS] */
+    void *scratch;
+} dnsplat_cloud_distances_args;
+typedef struct dnsplat_mesh_sample_args {
+    int64_t S;                  /* samples */
+    uint64_t seed;
+    int32_t V, T;
+    const double *cdf;          /* device [T]: the inclusive prefix sums of dnsplat_mesh_areas' areas */
+    const float *vertices;      /* [V,3] */
+    const int32_t *triangles;   /* [T,3] */
+    const float *face_normals;  /* [T,3] of dnsplat_mesh_areas */
+    float *points;              /* [S,3] */
+    float *normals;             /* [S,3] */
+    int32_t *faces;             /* [S] */
+} dnsplat_mesh_sample_args;
+size_t dnsplat_cloud_distances_scratch_bytes(int64_t M);   /* 0 for an invalid size */
+int dnsplat_cloud_distances(const dnsplat_cloud_distances_args *args, dnsplat_stream_t stream);
+int dnsplat_mesh_areas(int32_t V, const float *vertices, int32_t T, const int32_t *triangles, double *areas, float *face_normals,
+                       dnsplat_stream_t stream);
+int dnsplat_mesh_sample(const dnsplat_mesh_sample_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
