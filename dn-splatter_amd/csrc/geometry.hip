@@ -85,7 +85,8 @@ __global__ __launch_bounds__(GM_THREADS) void gm_search_kernel(GmSearch a)
     if (m < a.M) {
         DfList<1> L;
         const bool ok = df_search<1>(a.ix, a.src[m * 3], a.src[m * 3 + 1], a.src[m * 3 + 2], 1, L);
-        const bool found = ok && L.i[0] != 0x7fffffff;                           // no comparable target: every one of them has a nan
+        // no comparable target: every one of them has a nan or an inf coordinate (df_search keeps a row of d^2 = inf; it is no neighbour)
+        const bool found = ok && L.i[0] != 0x7fffffff && L.d[0] < (double)INFINITY;
         const int gi = found ? L.i[0] : -1;
         const double d2 = found ? L.d[0] : (double)NAN;
         const double d = sqrt(d2);

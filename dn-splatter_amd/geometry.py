@@ -88,7 +88,8 @@ def cloud_distances(src, tgt, src_normals=None, tgt_normals=None, threshold: flo
     float64, and with both normal arrays |n_src . n_tgt[idx]| of the normalised normals; the means, numpy's ``percentile`` of the
     distances, the shares ``d < threshold`` and ``d <= threshold``, min and max.  One ``dnsplat_cloud_distances`` call; float64 inputs
     are rounded to float32 once.  A source row with a non-finite coordinate gets ``idx = -1``, ``dist2 = nan`` and makes the means and the
-    percentile nan."""
+    percentile nan; a target row with a nan or inf coordinate is nobody's neighbour, and if every target is such a row, every source row
+    is non-finite."""
     if (src_normals is None) != (tgt_normals is None):
         raise ValueError("source and target normals are given together or not at all")
     if not 0.0 <= float(percentile) <= 100.0:

@@ -80,7 +80,8 @@ def squared_distance(q: Tensor, p: Tensor) -> Tensor:
 
 def nearest(tgt: Tensor, src: Tensor, chunk: int = 1024):
     """(idx int64 [M], d² float64 [M]): for every row of ``src`` the row of ``tgt`` of lowest (d², index), d² as ``squared_distance``.  A
-    source row with a non-finite coordinate, or one no target can be compared with, gets -1 and nan.  Brute force: the plain sum of
+    source row with a non-finite coordinate, or one no target can be compared with, gets -1 and nan; a target row with a nan or inf
+    coordinate (d² nan or inf) is compared with nobody, as include/dnsplat.h states.  Brute force: the plain sum of
     squares picks the candidates within 2^-48 relative of the row's minimum (it differs from the fused one by three roundings), the fused
     d² then ranks those."""
     N, M = tgt.shape[0], src.shape[0]

@@ -894,7 +894,8 @@ int dnsplat_mc_emit(const dnsplat_mc_args *args, dnsplat_stream_t stream);
  *   outputs    dist2 [M] double (required: the selection reads it back), idx [M] int32 or NULL, absdot [M] double or NULL.
  *   non-finite a source point with a nan or inf coordinate reads nothing: idx = -1, dist2 = absdot = nan; it counts in N_NONFINITE and
  *              makes the means, the percentile, min and max nan (numpy's behaviour on a nan distance).  The same holds for a point
- *              that no target can be compared with (every target has a nan coordinate).
+ *              that no target can be compared with: a target with a nan or inf coordinate (d2 nan or inf) is nobody's neighbour, so
+ *              finite targets win over it, and where every target has one, every source point is such a row (scipy refuses the data).
  *   scalars    device double [DNSPLAT_GEOM_COUNT] at the DNSPLAT_GEOM_* indices: the means of d = sqrt(d2), of d2 and of absdot (nan
  *              without normals), the percentile, the shares d < threshold (calculate_completeness) and d <= threshold
  *              (get_threshold_percentage: precision and recall), min d, max d, and the two order statistics of d2 the percentile was

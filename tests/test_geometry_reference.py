@@ -256,3 +256,87 @@ def test_count_from_the_area(tg):
     v, t = (torch.from_numpy(x) for x in inputs.square_with_degenerate())
     points, _, _ = tg.sample_mesh_surface(v, t, samples_per_area=1e3)
     assert points.shape[0] == 1000
+
+
+# ---- the builders of tests/test_gpu_geometry_edges.py ----------------------------------------------------------------------------------
+# What the GPU cases rest on is proven here from the restatement, without a GPU: the lattice's d² patterns, where sorted neighbours
+# split, which sources sit on the threshold, and what the restatement makes of the sampler's edge meshes.
+
+ROUND_BITS = inputs.ROUND_BITS
+LATTICE_CASES = {"plain": dict(m=4097, seed=71), "mixed": dict(m=4097, seed=72, a_values=(0, 1, 2, 4096), far=5),
+                 "wide": dict(m=65537, seed=73, a_values=tuple(range(8)), n_j=64, n_i=64)}
+
+
+@pytest.mark.parametrize("name", list(LATTICE_CASES))
+def test_distance_lattice_patterns_are_exact(tg, name):
+    src, tgt, patterns, triples = inputs.distance_lattice(**LATTICE_CASES[name])
+    m = LATTICE_CASES[name]["m"]
+    assert src.dtype == np.float32 and src.shape == (m, 3) and tgt.shape == (3, 3) and patterns.shape == (m,)
+    d2 = tg.squared_distance(torch.from_numpy(src), torch.from_numpy(tgt[0]))
+    assert np.array_equal(d2.numpy().view(np.int64), patterns), "the integer derivation of the pattern is not the restatement's d²"
+    idx, near = tg.nearest(torch.from_numpy(tgt), torch.from_numpy(src))
+    assert not bool(idx.any()), "the origin is not every source's nearest target"
+    assert np.array_equal(near.numpy().view(np.int64), patterns)
+
+
+def test_distance_lattice_drives_the_late_rounds():
+    _, _, patterns, triples = inputs.distance_lattice(**LATTICE_CASES["plain"])
+    assert len(set((patterns >> 20).tolist())) == 1, "the plain lattice differs above bit 20"
+    assert len(set(patterns.tolist())) == 1024 >= 900
+    a, j, i = triples.T
+    assert not a.any() and np.array_equal(patterns, inputs.LATTICE_ONE | ((j * j) << 10) | (i * i))
+    assert np.bincount(np.unique(patterns, return_counts=True)[1])[2:].sum() > 900, "fewer than 900 values are drawn more than once"
+    srt = np.sort(patterns)
+    rounds = {inputs.split_round(p, q, ROUND_BITS) for p, q in zip(srt[:-1], srt[1:])}
+    assert rounds == {4, 5, 6}, rounds                                 # 6: equal neighbours
+
+
+def test_mixed_lattice_splits_in_every_round():
+    _, _, patterns, triples = inputs.distance_lattice(**LATTICE_CASES["mixed"])
+    srt = np.sort(patterns)
+    rounds = {inputs.split_round(p, q, ROUND_BITS) for p, q in zip(srt[:-1], srt[1:])}
+    assert rounds == {0, 1, 2, 3, 4, 5, 6}, rounds
+    assert (triples[:5] == -1).all() and (srt[-5:] == np.sort(patterns[:5])).all(), "the far sources are not the five largest"
+    assert inputs.split_round(srt[-6], srt[-5], ROUND_BITS) == 0
+    one = inputs.LATTICE_ONE
+    assert inputs.split_round(one, one, ROUND_BITS) == 6 and inputs.split_round(one, one + 1, ROUND_BITS) == 5
+    assert [inputs.split_round(one, one ^ (1 << b), ROUND_BITS) for b in (9, 10, 19, 20, 30, 31, 41, 42, 52, 53)] == [5, 4, 4, 3, 3, 2, 2, 1, 1, 0]
+
+
+def test_lattice_sources_on_the_threshold():
+    """d = sqrt(d²) is exactly 1 for the triples (0, 0, 0) and (0, 0, 1) — sqrt(1 + 2^-52) rounds to 1 — and above 1 for every other."""
+    _, _, patterns, triples = inputs.distance_lattice(**LATTICE_CASES["plain"])
+    d = np.sqrt(patterns.view(np.float64))
+    on = (triples[:, 0] == 0) & (triples[:, 1] == 0) & (triples[:, 2] <= 1)
+    assert np.array_equal(d <= 1.0, on) and not (d < 1.0).any()
+    assert int((triples == 0).all(axis=1).sum()) >= 1 and int(on.sum()) > int((triples == 0).all(axis=1).sum())
+
+
+def test_rank_percentile_lands_between_two_ranks():
+    for n in (2, 513, 4097, 65537):
+        for k in (0, n // 3, n - 2):
+            h = (n - 1) * (inputs.rank_percentile(k, n) / 100.0)
+            assert int(np.floor(h)) == k and 0.25 < h - k < 0.75
+
+
+def test_sampler_edge_meshes(tg):
+    v, t = (torch.from_numpy(x) for x in inputs.collinear_mesh())
+    areas, normals = tg.mesh_areas(v, t)
+    assert areas.tolist() == [0.0, 0.0, 0.0] and not bool(normals.any())
+    cdf = torch.cumsum(areas, 0)
+    for last in (0.0, float("nan"), float("inf"), -1.0):
+        c = cdf.clone()
+        c[-1] = last
+        points, point_normals, faces = tg.mesh_sample(65, 9, c, v, t, normals)
+        assert bool((faces == -1).all()) and bool(torch.isnan(points).all()) and not bool(point_normals.any())
+    v, t = (torch.from_numpy(x) for x in inputs.square_between_degenerates())
+    areas, normals = tg.mesh_areas(v, t)
+    assert areas.tolist() == [0.0, 0.0, 0.5, 0.0, 0.5, 0.0, 0.0]
+    _, _, faces = tg.sample_mesh_surface(v, t, count=70_000, seed=9)
+    counts = np.bincount(faces.numpy(), minlength=7)
+    assert counts[[0, 1, 3, 5, 6]].sum() == 0 and abs(counts[2] - 35_000) <= 6 * np.sqrt(70_000 * 0.25)
+    v, t = (torch.from_numpy(x) for x in inputs.one_triangle())
+    points, _, faces = tg.sample_mesh_surface(v, t, count=257, seed=9)
+    assert not bool(faces.any())
+    bary = tg.barycentrics(points, v, t, faces)
+    assert float(bary.min()) >= -1e-6 and float(bary.max()) <= 1 + 1e-6

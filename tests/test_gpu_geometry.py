@@ -62,8 +62,9 @@ def rel(a, b):
     return 0.0 if a == b else abs(a - b) / abs(b)
 
 
-def compare(tg, got, want, normals=True):
-    """One direction of the device against the restatement's dictionary."""
+def compare(tg, got, want, normals=True, means=True):
+    """One direction of the device against the restatement's dictionary.  ``means=False`` leaves the three means to the caller: REL is
+    stated for the few partials of the sizes here (tests/test_gpu_geometry_edges.py holds them to a derived bound past one fold trip)."""
     g = tg.GEOM_INDEX
     assert got.idx.dtype == torch.int32 and torch.equal(got.idx.long(), want["idx"])
     assert torch.equal(bits(got.dist2), bits(want["dist2"]))
@@ -71,14 +72,14 @@ def compare(tg, got, want, normals=True):
     gs, ws = got.scalars.tolist(), want["scalars"].tolist()
     for k in ("order_lo_d2", "order_hi_d2"):
         assert np.float64(gs[g[k]]).view(np.int64) == np.float64(ws[g[k]]).view(np.int64), k
-    for k in ("mean_d", "mean_d2", "percentile", "min_d", "max_d"):
+    for k in ("mean_d", "mean_d2", "percentile", "min_d", "max_d")[0 if means else 2:]:
         print(k, gs[g[k]], ws[g[k]], rel(gs[g[k]], ws[g[k]]) / 2.0 ** -52)
         assert rel(gs[g[k]], ws[g[k]]) <= REL, k
     assert gs[g["share_lt"]] == ws[g["share_lt"]] and gs[g["share_le"]] == ws[g["share_le"]]
     assert gs[10:] == [0.0, 0.0]
     if normals:
         assert float((got.absdot - want["absdot"]).abs().max()) <= 8 * 2.0 ** -53
-        assert rel(gs[g["mean_absdot"]], ws[g["mean_absdot"]]) <= REL
+        assert not means or rel(gs[g["mean_absdot"]], ws[g["mean_absdot"]]) <= REL
     else:
         assert got.absdot is None and np.isnan(gs[g["mean_absdot"]])
 
