@@ -35,6 +35,8 @@ from .marching import marching_cubes, marching_cubes_mesh, mcubes_marching_cubes
 from . import geometry, torch_geometry  # noqa: F401
 from .geometry import (PDMetrics, calculate_accuracy, calculate_completeness, cloud_distances, cloud_metrics, install_pd_metrics,  # noqa: F401
                        mesh_metrics, sample_mesh_surface)
+from . import mesh_cull, torch_mesh_cull  # noqa: F401
+from .mesh_cull import cull_mesh, culled_mesh_metrics, cut_mesh, render_mesh_depth, vertex_visibility  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -47,5 +49,6 @@ __all__ = [
     "marching", "torch_marching", "marching_cubes", "marching_cubes_mesh", "mcubes_marching_cubes",
     "geometry", "torch_geometry", "PDMetrics", "calculate_accuracy", "calculate_completeness", "cloud_distances", "cloud_metrics",
     "install_pd_metrics", "mesh_metrics", "sample_mesh_surface",
+    "mesh_cull", "torch_mesh_cull", "cull_mesh", "culled_mesh_metrics", "cut_mesh", "render_mesh_depth", "vertex_visibility",
     "build_library", "load_library", "DnsplatError",
 ]

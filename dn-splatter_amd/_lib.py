@@ -217,6 +217,32 @@ class MeshSampleArgs(ctypes.Structure):
     ]
 
 
+class MeshDepthArgs(ctypes.Structure):
+    _fields_ = [
+        ("V", c_int32), ("T", c_int32), ("C", c_int32), ("width", c_int32), ("height", c_int32),
+        ("vertices", c_void_p), ("triangles", c_void_p), ("w2c", c_void_p),
+        ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+        ("znear", ctypes.c_double), ("zfar", ctypes.c_double), ("depth", c_void_p), ("scratch", c_void_p), ("stats", c_void_p),
+    ]
+
+
+class MeshVisibilityArgs(ctypes.Structure):
+    _fields_ = [
+        ("V", c_int32), ("C", c_int32), ("width", c_int32), ("height", c_int32), ("vertices", c_void_p), ("w2c", c_void_p),
+        ("K", ctypes.c_double * 9), ("rendered", c_void_p), ("depth_gt", c_void_p),
+        ("remove_occlusion", c_int32), ("remove_missing_depth", c_int32), ("obs", c_void_p), ("invalid", c_void_p),
+    ]
+
+
+class MeshCutArgs(ctypes.Structure):
+    _fields_ = [
+        ("V", c_int32), ("T", c_int32), ("vertices", c_void_p), ("triangles", c_void_p), ("obs", c_void_p), ("invalid", c_void_p),
+        ("obs_threshold", c_int32), ("invalid_share", ctypes.c_double), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
+        ("counts", c_void_p), ("cap_v", c_int64), ("cap_t", c_int64),
+        ("out_vertices", c_void_p), ("out_triangles", c_void_p), ("status", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -247,6 +273,9 @@ EXPORTS = [
     "dnsplat_mc_scratch_bytes", "dnsplat_mc_count", "dnsplat_mc_emit",
     # likewise: the geometry scores (cloud distances, mesh areas and samples)
     "dnsplat_cloud_distances_scratch_bytes", "dnsplat_cloud_distances", "dnsplat_mesh_areas", "dnsplat_mesh_sample",
+    # likewise: the mesh visibility culling (depth renders, vertex votes, the cut)
+    "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_depth", "dnsplat_mesh_visibility", "dnsplat_mesh_cut_scratch_bytes",
+    "dnsplat_mesh_cut_count", "dnsplat_mesh_cut_emit",
 ]
 
 _lib = None
@@ -355,11 +384,20 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_cloud_distances.argtypes = [ctypes.POINTER(CloudDistancesArgs), c_void_p]
         L.dnsplat_mesh_areas.argtypes = [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
         L.dnsplat_mesh_sample.argtypes = [ctypes.POINTER(MeshSampleArgs), c_void_p]
+        L.dnsplat_mesh_depth_scratch_bytes.restype = c_size_t
+        L.dnsplat_mesh_depth_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_mesh_depth.argtypes = [ctypes.POINTER(MeshDepthArgs), c_void_p]
+        L.dnsplat_mesh_visibility.argtypes = [ctypes.POINTER(MeshVisibilityArgs), c_void_p]
+        L.dnsplat_mesh_cut_scratch_bytes.restype = c_size_t
+        L.dnsplat_mesh_cut_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_mesh_cut_count.argtypes = [ctypes.POINTER(MeshCutArgs), c_void_p]
+        L.dnsplat_mesh_cut_emit.argtypes = [ctypes.POINTER(MeshCutArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
                             "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
-                            "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes"):
+                            "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
+                            "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

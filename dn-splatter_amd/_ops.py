@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, MeshSampleArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, MeshCutArgs, MeshDepthArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -444,6 +444,43 @@ def _mesh_sample_args(seed, cdf, vertices, triangles, face_normals, points, norm
     a.V, a.T = vertices.shape[0], triangles.shape[0]
     a.cdf, a.vertices, a.triangles, a.face_normals = _ptr(cdf), _ptr(vertices), _ptr(triangles), _ptr(face_normals)
     a.points, a.normals, a.faces = _ptr(points), _ptr(normals), _ptr(faces)
+    return a
+
+
+def _mesh_depth_args(vertices, triangles, w2c, k, width, height, znear, zfar, depth, scratch, stats=None):
+    a = MeshDepthArgs()
+    a.V, a.T, a.C = vertices.shape[0], triangles.shape[0], w2c.shape[0]
+    a.width, a.height = width, height
+    a.vertices, a.triangles, a.w2c = _ptr(vertices), _ptr(triangles), _ptr(w2c)
+    a.fx, a.fy, a.cx, a.cy = k[0], k[4], k[2], k[5]
+    a.znear, a.zfar = znear, zfar
+    a.depth, a.scratch, a.stats = _ptr(depth), _ptr(scratch), _ptr(stats)
+    return a
+
+
+def _mesh_visibility_args(vertices, w2c, k, width, height, rendered, depth_gt, remove_occlusion, remove_missing_depth, obs, invalid):
+    a = MeshVisibilityArgs()
+    a.V, a.C = vertices.shape[0], w2c.shape[0]
+    a.width, a.height = width, height
+    a.vertices, a.w2c = _ptr(vertices), _ptr(w2c)
+    a.K = (ctypes.c_double * 9)(*k)
+    a.rendered, a.depth_gt = _ptr(rendered), _ptr(depth_gt)
+    a.remove_occlusion, a.remove_missing_depth = int(remove_occlusion), int(remove_missing_depth)
+    a.obs, a.invalid = _ptr(obs), _ptr(invalid)
+    return a
+
+
+def _mesh_cut_args(vertices, triangles, obs, invalid, obs_threshold, invalid_share, scratch, counts, out_vertices=None, out_triangles=None,
+                   status=None):
+    a = MeshCutArgs()
+    a.V, a.T = vertices.shape[0], triangles.shape[0]
+    a.vertices, a.triangles, a.obs, a.invalid = _ptr(vertices), _ptr(triangles), _ptr(obs), _ptr(invalid)
+    a.obs_threshold, a.invalid_share = obs_threshold, invalid_share
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.counts = _ptr(counts)
+    a.cap_v = 0 if out_vertices is None else out_vertices.shape[0]
+    a.cap_t = 0 if out_triangles is None else out_triangles.shape[0]
+    a.out_vertices, a.out_triangles, a.status = _ptr(out_vertices), _ptr(out_triangles), _ptr(status)
     return a
 
 

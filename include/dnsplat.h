@@ -62,7 +62,9 @@ extern "C" {
  * dnsplat_level_rays / dnsplat_level_points / dnsplat_level_rays_args / dnsplat_level_points_args: the level-set surface points;
  * dnsplat_mc_scratch_bytes / dnsplat_mc_count / dnsplat_mc_emit / dnsplat_mc_args: marching cubes on a lattice;
  * dnsplat_cloud_distances / dnsplat_cloud_distances_scratch_bytes / dnsplat_cloud_distances_args / dnsplat_mesh_areas /
- * dnsplat_mesh_sample / dnsplat_mesh_sample_args: the geometry scores). */
+ * dnsplat_mesh_sample / dnsplat_mesh_sample_args: the geometry scores; dnsplat_mesh_depth / dnsplat_mesh_depth_scratch_bytes /
+ * dnsplat_mesh_depth_args / dnsplat_mesh_visibility / dnsplat_mesh_visibility_args / dnsplat_mesh_cut_scratch_bytes /
+ * dnsplat_mesh_cut_count / dnsplat_mesh_cut_emit / dnsplat_mesh_cut_args: the mesh visibility culling in front of them). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -981,6 +983,99 @@ int dnsplat_cloud_distances(const dnsplat_cloud_distances_args *args, dnsplat_st
 int dnsplat_mesh_areas(int32_t V, const float *vertices, int32_t T, const int32_t *triangles, double *areas, float *face_normals,
                        dnsplat_stream_t stream);
 int dnsplat_mesh_sample(const dnsplat_mesh_sample_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ mesh visibility culling (added after ABI 15, found by symbol)
+ * cull_mesh of the reference (eval/eval_mesh_vis_cull.py:176-266, the step in front of compute_metrics): the double-sided depth renders
+ * of the mesh (pyrender through OpenGL there), the per-vertex votes of cull_from_one_pose summed over the poses, the triangle rule with
+ * remove_unreferenced_vertices.  Everything is caller-allocated; nothing is read on the host, allocated or synchronised; no
+ * floating-point atomic: equal inputs give equal bits.  Double arithmetic, every sum associated as written, no contraction.
+ * w2c is device double [C,12]: the rows of the OpenCV world-to-camera [R | t] per camera (the binding derives it from the reference's
+ * OpenGL camera-to-world poses: columns 1 and 2 negated, then the analytic inverse).
+ *
+ * dnsplat_mesh_depth — depth[c][v][u] (float32 [C,H,W]) = the smallest camera-space z in [znear, zfar] at which the ray through the pixel
+ *   centre (u + 0.5, v + 0.5) meets a triangle, either winding; 0 where there is none.  Per (camera, triangle):
+ *   p_i = ((R_k0 x + R_k1 y) + R_k2 z) + t_k from the exactly converted vertices; c0 = p1 x p2, c1 = p2 x p0, c2 = p0 x p1,
+ *   n = (c1 + c2) + c0, D = (p0.x c0.x + p0.y c0.y) + p0.z c0.z.  Per pixel: d = (((u + 0.5) - cx) / fx, ((v + 0.5) - cy) / fy),
+ *   E_i = (c_i.x d.x + c_i.y d.y) + c_i.z and S likewise from n; inside iff (every E_i >= 0 or every E_i <= 0) and S != 0; z = D / S;
+ *   a hit iff znear <= z <= zfar; the map holds the minimum of float32(z), taken as an unsigned integer minimum of its bits (the
+ *   buffer starts as +inf; a last pass writes 0 where +inf remained).  Triangles crossing z = 0 need no clipping: their z is rejected.
+ *   Swapping two indices of a triangle changes no bit; neither does the order of the triangles.  A triangle with an index outside
+ *   [0, V), a repeated index, a non-finite vertex or an area (dnsplat_mesh_areas') that is not positive and finite covers nothing.
+ *   Each triangle searches a pixel box that bounds its part with z >= znear, widened by a pixel: a search window, not part of the result.
+ *   scratch: dnsplat_mesh_depth_scratch_bytes(width, height) bytes, 8-byte aligned (the pixel rays).  stats: NULL, or device uint64 [3]
+ *   to which the call ADDS {triangle setups with a non-empty box, accepted fragments, issued atomics} (a measurement aid).
+ *   Four launches.  PARITY UNPINNED against pyrender, whose 24-bit z-buffer quantises what this states exactly.
+ *   Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL args / vertices / triangles / w2c / depth / scratch, V, T, C, width or
+ *   height < 1, fx or fy 0 or nan, not 0 < znear <= zfar < inf; DNSPLAT_ERR_UNSUPPORTED for width height > 2^31 - 1 or C > 65535;
+ *   DNSPLAT_ERR_WORKSPACE for a misaligned scratch.
+ *
+ * dnsplat_mesh_visibility — get_grid_culling_pattern: per vertex, one thread, over the C cameras: p as above,
+ *   q_k = (K_k0 p.x + K_k1 p.y) + K_k2 p.z, pz = q_2 + 1e-8, px = q_0 / pz, py = q_1 / pz;
+ *   in_frustum = 0 <= px <= W - 1 and 0 <= py <= H - 1 and pz > 0; u, v = px, py truncated;
+ *   obs += in_frustum and (remove_occlusion ? pz < (double)(rendered[c][v][u] + 0.02f) : 1)     (numpy adds to a float32 map in float32)
+ *   invalid += in_frustum and remove_missing_depth and depth_gt[c][v][u] <= 0.
+ *   obs / invalid are int32 [V] and ACCUMULATE: the caller zeroes them once and chains camera batches.  One launch.
+ *   Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL args / vertices / w2c / obs / invalid, a map whose flag is set and
+ *   whose pointer is NULL, V, C, width or height < 1; DNSPLAT_ERR_UNSUPPORTED for width height > 2^31 - 1.
+ *
+ * dnsplat_mesh_cut_count / dnsplat_mesh_cut_emit — the rule of :251-260 and remove_unreferenced_vertices.  A triangle is kept iff some
+ *   vertex has obs > obs_threshold and not every vertex has (double)invalid > invalid_share * (double)obs; a triangle with an index
+ *   outside [0, V) is not kept.  Kept triangles stay in their order, the vertices they reference stay in theirs, indices are remapped.
+ *   count: counts = {V', T'} (device int64 [2]) and the marks, flags and scanned block counts in scratch
+ *   (dnsplat_mesh_cut_scratch_bytes(V, T) bytes, 4-byte aligned).  One memset and three launches.
+ *   emit, after count with the same arguments: the first min(V', cap_v) vertices and min(T', cap_t) triangles, nothing past a capacity;
+ *   *status = DNSPLAT_MESH_CUT_STATUS_VERTICES if V' > cap_v | DNSPLAT_MESH_CUT_STATUS_TRIANGLES if T' > cap_t.  Two launches; it may
+ *   be repeated.  Integers only, no atomics.  Returns without a launch: DNSPLAT_ERR_INVALID_ARG for a NULL args / vertices / triangles /
+ *   obs / invalid / scratch / counts (emit: / status, / a buffer whose capacity is positive), V or T < 1, a negative capacity;
+ *   DNSPLAT_ERR_WORKSPACE for a short or misaligned scratch. */
+#define DNSPLAT_MESH_CUT_STATUS_VERTICES 1
+#define DNSPLAT_MESH_CUT_STATUS_TRIANGLES 2
+typedef struct dnsplat_mesh_depth_args {
+    int32_t V, T, C;
+    int32_t width, height;
+    const float *vertices;      /* [V,3] */
+    const int32_t *triangles;   /* [T,3] */
+    const double *w2c;          /* [C,12] */
+    double fx, fy, cx, cy;
+    double znear, zfar;
+    float *depth;               /* [C,height,width] */
+    void *scratch;
+    uint64_t *stats;            /* NULL or device [3], added to */
+} dnsplat_mesh_depth_args;
+typedef struct dnsplat_mesh_visibility_args {
+    int32_t V, C;
+    int32_t width, height;
+    const float *vertices;      /* [V,3] */
+    const double *w2c;          /* [C,12] */
+    double K[9];                /* row-major 3x3 */
+    const float *rendered;      /* [C,height,width]; read iff remove_occlusion */
+    const float *depth_gt;      /* [C,height,width]; read iff remove_missing_depth */
+    int32_t remove_occlusion, remove_missing_depth;
+    int32_t *obs;               /* [V], added to */
+    int32_t *invalid;           /* [V], added to */
+} dnsplat_mesh_visibility_args;
+typedef struct dnsplat_mesh_cut_args {
+    int32_t V, T;
+    const float *vertices;      /* [V,3] */
+    const int32_t *triangles;   /* [T,3] */
+    const int32_t *obs;         /* [V] */
+    const int32_t *invalid;     /* [V] */
+    int32_t obs_threshold;      /* the reference: 3 */
+    double invalid_share;       /* the reference: 0.7 */
+    void *scratch;
+    size_t scratch_bytes;
+    int64_t *counts;            /* device int64 [2]: V', T'; written by count, read by emit */
+    int64_t cap_v, cap_t;       /* emit: rows of out_vertices / out_triangles */
+    float *out_vertices;        /* emit: [cap_v,3] */
+    int32_t *out_triangles;     /* emit: [cap_t,3] */
+    int32_t *status;            /* emit: device int32 [1] */
+} dnsplat_mesh_cut_args;
+size_t dnsplat_mesh_depth_scratch_bytes(int32_t width, int32_t height);   /* 0 for an invalid size */
+int dnsplat_mesh_depth(const dnsplat_mesh_depth_args *args, dnsplat_stream_t stream);
+int dnsplat_mesh_visibility(const dnsplat_mesh_visibility_args *args, dnsplat_stream_t stream);
+size_t dnsplat_mesh_cut_scratch_bytes(int32_t V, int32_t T);   /* 0 for an invalid size */
+int dnsplat_mesh_cut_count(const dnsplat_mesh_cut_args *args, dnsplat_stream_t stream);
+int dnsplat_mesh_cut_emit(const dnsplat_mesh_cut_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
