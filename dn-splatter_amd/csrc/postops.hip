@@ -114,11 +114,14 @@ __global__ __launch_bounds__(256) void densify_classify_kernel(dnsplat_densify_a
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.N) return;
     const float s0 = a.scales[3 * g], s1 = a.scales[3 * g + 1], s2 = a.scales[3 * g + 2];
-    const float smax = fmaxf(fmaxf(expf(s0), expf(s1)), expf(s2));                       // scales.exp().max(dim=-1)
+    // scales.exp().max(dim=-1).  torch's max propagates a nan where fmaxf returns the other operand: a nan log-scale makes all
+    // three maxima nan, and every scale comparison below false, as in the reference
+    const bool nan_scale = s0 != s0 || s1 != s1 || s2 != s2;
+    const float smax = nan_scale ? __builtin_nanf("") : fmaxf(fmaxf(expf(s0), expf(s1)), expf(s2));
     const float z = a.max_2Dsize ? a.max_2Dsize[g] : 0.f;
     // a split child holds log(exp(s) / 1.6) (split_gaussians); whoever looks at it later exponentiates that again
     const float c0 = expf(logf(expf(s0) / 1.6f)), c1 = expf(logf(expf(s1) / 1.6f)), c2 = expf(logf(expf(s2) / 1.6f));
-    const float smax_child = fmaxf(fmaxf(c0, c1), c2);
+    const float smax_child = nan_scale ? __builtin_nanf("") : fmaxf(fmaxf(c0, c1), c2);
     float smax_dup = smax;
     uint8_t f = 0;
     if (a.do_densify) {

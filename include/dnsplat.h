@@ -403,7 +403,10 @@ int dnsplat_densify_stats(int32_t N, const int32_t *radii, const float *xy_grads
 /* Densification decisions of refinement_after (dn_model.py:271-386; cull rules of the inherited nerfstudio
  * SplatfactoModel.cull_gaussians), one flag byte per Gaussian.  do_densify = the `do_densification` branch is active;
  * screen_rules = step < stop_screen_size_at; cull_big = step > refine_every * reset_alpha_every.  Appended entries (split
- * children, duplicates) enter the cull with max_2Dsize = 0, children with scales log(exp(s) / 1.6). */
+ * children, duplicates) enter the cull with max_2Dsize = 0, children with scales log(exp(s) / 1.6).
+ * Every comparison is the reference's, strictness included (>, <, and <= for the duplicate rule), and nan follows torch: a nan
+ * log-scale makes the Gaussian's largest scale nan (torch's max propagates it), so none of its scale comparisons holds — it is
+ * neither split, duplicated nor too big; a nan opacity is not low; 0 / 0 visibility is not a high gradient. */
 #define DNSPLAT_DENSIFY_SPLIT 1       /* split into n_split_samples children; the parent is then pruned */
 #define DNSPLAT_DENSIFY_DUP 2         /* duplicated once */
 #define DNSPLAT_DENSIFY_CULL 4        /* the original entry is removed */

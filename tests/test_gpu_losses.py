@@ -15,8 +15,8 @@ import functools
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+from _postops_ref import _restated_surface_normal, surface_normal_allowance
 from _scenes import FP32_ENVELOPE, PIX_MAX, PIX_P99, assert_close, check_pixels, fp64_envelope, row_rel_stats
 
 pytestmark = pytest.mark.gpu
@@ -402,23 +402,6 @@ def test_scale_reg_of_no_gaussians_is_nan(dns):
 # ---- depth -> surface normal (dnsplat_dn_depth_normals) ---------------------------------------------------------------------------
 
 
-def _restated_surface_normal(depth, alphas, fx, fy, cx, cy, dtype):
-    """dn_model.py:533-537 (alpha == 0: the image-wide maximum depth) and :589-603 through model.normal_from_depth_image."""
-    from dn_splatter_amd import model
-
-    H, W = depth.shape
-    d = depth.to(dtype)
-    filled = torch.where(alphas > 0, d, d.max())
-    if dtype == torch.float32:
-        n = model.normal_from_depth_image(filled[..., None], fx, fy, cx, cy, (W, H), torch.eye(4, device=depth.device))
-    else:                       # the same back-projection (c2w = identity) in float64: normal_from_depth_image computes in float32
-        gx = torch.arange(W, dtype=dtype, device=depth.device)[None, :] + 0.5
-        gy = torch.arange(H, dtype=dtype, device=depth.device)[:, None] + 0.5
-        n = model.pcd_to_normal(torch.stack([(gx - cx) * filled / fx, (gy - cy) * filled / fy, filled], dim=-1))
-    n = n @ torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=dtype, device=depth.device))
-    return filled, (1 + n) / 2
-
-
 @pytest.mark.parametrize("workload", ["c2", "c3"])
 def test_depth_normals_match_fp64(dns, workload):
     """dnsplat_dn_depth_normals on a rendered depth (the C2 / C3 scene at its full frame) with alpha == 0 regions added: the fill
@@ -459,14 +442,9 @@ def test_depth_normals_match_fp64(dns, workload):
     border = torch.ones(H, W, dtype=torch.bool, device=DEV)
     border[1:-1, 1:-1] = False
     assert bool((sn[border] == 0.5).all())
-    # The restatement's fp32 error is cancellation in (x +- 1 - cx) d / fx away from the image centre (up to ~5e-5 at fx = 1200).
-    # The kernel rounds the same products but multiplies by 1 / fx instead of dividing, so at a given entry the two fp32 errors need
-    # not be alike even where their sizes are: the envelope is the restatement's worst error over the pixel's 3 x 3 stencil support
-    # and its channels (a pixel-by-pixel envelope leaves the kernel ~4x over it at a few thousand entries of a 1080p frame).
-    e32 = (sn32.double() - sn64).abs().amax(dim=-1)[None, None]
-    env = FP32_ENVELOPE * F.max_pool2d(e32, 3, 1, 1)[0, 0][..., None]
+    # 5e-6 + the envelope of the restatement's own fp32 error over the pixel's 3 x 3 stencil support (_postops_ref)
+    allow, e32 = surface_normal_allowance(sn32, sn64)
     d = (sn.double() - sn64).abs()
-    allow = 5e-6 + env
     ratio = float((d / allow).max())
     print(f"[losses] surface normal {workload}: max error {float(d.max()):.2e} (fp32 restatement {float(e32.max()):.2e}); "
           f"{int((d > 5e-6).sum())} of {d.numel()} entries beyond the 5e-6 floor; worst error / allowance {ratio:.3f}")
