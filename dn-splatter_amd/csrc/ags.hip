@@ -12,13 +12,13 @@
 //                       (one pixel for the Laplacian, one more for the dilation), then the threshold bits of the tile plus one pixel,
 //                       three bits to a byte; each thread then ORs 3 x 3 bytes and finishes its own four pixels.  Mode 1 needs no
 //                       neighbour.  One partial (two sums in double, one integer count) per workgroup;
-//   ags_fold_kernel     one workgroup adds the partials in a fixed order.
+//   ags_fold_kernel     one workgroup adds the partials in the fixed order of block_reduce.h (dns_block_join, dns_fold_partials).
 // No atomic and no floating-point sum whose order depends on scheduling: equal inputs give equal bits.  The normaliser 1 / count is
 // only known here on the device; the caller divides there.  Compiled without contraction: 2 x - 1, n + 1e-6, the correctly rounded
 // 1 / x and the five-term sum are the fp32 operations torch performs, in the order  ((up + down) + left) + right - 4 r.
 // Traffic: 36 B read and 24 B written per pixel (plus the halo's share of the ground truth, from cache).
 
-#include "splat_common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -27,7 +27,6 @@ constexpr int AG_TW = 64, AG_TH = 16;                    // the tile: thread t o
 constexpr int AG_PER = AG_TW * AG_TH / AG_THREADS;       // pixels per thread
 constexpr int AG_RW = AG_TW + 4, AG_RH = AG_TH + 4;      // reciprocals: the tile and two pixels around it
 constexpr int AG_EW = AG_TW + 2, AG_EH = AG_TH + 2;      // threshold bits: the tile and one pixel around it
-constexpr int AG_FOLD = AG_THREADS;                      // partials the fold kernel takes per trip
 constexpr float AG_EPS = 1e-6f;                          // find_edges: 1 / (im + 1e-6)
 constexpr float AG_EDGE = 0.01f;                         // find_edges: threshold
 constexpr float AG_COS = 0.99500416527802577f;           // cos(0.1): arccos(d) > 0.1  <=>  d < cos(0.1)
@@ -35,6 +34,8 @@ constexpr float AG_COS = 0.99500416527802577f;           // cos(0.1): arccos(d) 
 struct AgsPartial {                                      // 24 bytes
     double a, b;
     long long n;
+    static __device__ AgsPartial identity() { return AgsPartial{0.0, 0.0, 0}; }
+    __device__ void join(const AgsPartial &o) { a += o.a; b += o.b; n += o.n; }
 };
 
 template <bool HWC>
@@ -96,8 +97,7 @@ __global__ __launch_bounds__(AG_THREADS) void ags_normal_kernel(int W, int H, in
 
     const int tx = t & (AG_TW - 1), ty = t / AG_TW;
     const int x = x0 + tx;
-    double sum_a = 0.0, sum_b = 0.0;
-    long long n = 0;
+    AgsPartial v = AgsPartial::identity();
 #pragma unroll
     for (int k = 0; k < AG_PER; ++k) {
         const int ly = ty + k * (AG_THREADS / AG_TW);
@@ -130,52 +130,29 @@ __global__ __launch_bounds__(AG_THREADS) void ags_normal_kernel(int W, int H, in
         for (int c = 0; c < 3; ++c) {
             const float ds = __fsub_rn(s[c], g[c]), dp = __fsub_rn(p[c], g[c]);
             const bool in = (keep >> c) & 1u;
-            if (in) { sum_a += (double)fabsf(ds); ++n; }
-            sum_b += (double)fabsf(dp);
+            if (in) { v.a += (double)fabsf(ds); ++v.n; }
+            v.b += (double)fabsf(dp);
             const size_t at = ag_index<HWC>(c, y, x, W, P);
             if (v_surf) v_surf[at] = in ? __fmul_rn(w_surf, ag_sign(ds)) : 0.f;
             if (v_pred) v_pred[at] = __fmul_rn(w_pred, ag_sign(dp));
         }
     }
 
-#pragma unroll
-    for (int off = DNS_WAVE / 2; off >= 1; off >>= 1) {
-        sum_a += __shfl_xor(sum_a, off, DNS_WAVE);
-        sum_b += __shfl_xor(sum_b, off, DNS_WAVE);
-        n += __shfl_xor(n, off, DNS_WAVE);
-    }
-    if ((t & (DNS_WAVE - 1)) == 0) { red[t / DNS_WAVE].a = sum_a; red[t / DNS_WAVE].b = sum_b; red[t / DNS_WAVE].n = n; }
-    __syncthreads();
-    if (t == 0) {
-        AgsPartial out;
-        out.a = (red[0].a + red[1].a) + (red[2].a + red[3].a);
-        out.b = (red[0].b + red[1].b) + (red[2].b + red[3].b);
-        out.n = (red[0].n + red[1].n) + (red[2].n + red[3].n);
-        part[blockIdx.x] = out;
-    }
+    dns_block_join<AG_THREADS>(v, red);
+    if (t == 0) part[blockIdx.x] = v;
 }
 
-// the partials of all workgroups, added in one fixed order: thread t takes t, t + AG_FOLD, ..., then the tree of the main kernel
+// the partials of all workgroups, added in the one fixed order of dns_fold_partials (block_reduce.h)
 __global__ __launch_bounds__(AG_THREADS) void ags_fold_kernel(int n_part, const AgsPartial *__restrict__ part, double *__restrict__ sums,
                                                                int64_t *__restrict__ count)
 {
     __shared__ AgsPartial red[AG_THREADS / DNS_WAVE];
-    const int t = threadIdx.x;
-    double sum_a = 0.0, sum_b = 0.0;
-    long long n = 0;
-    for (int i = t; i < n_part; i += AG_FOLD) { sum_a += part[i].a; sum_b += part[i].b; n += part[i].n; }
-#pragma unroll
-    for (int off = DNS_WAVE / 2; off >= 1; off >>= 1) {
-        sum_a += __shfl_xor(sum_a, off, DNS_WAVE);
-        sum_b += __shfl_xor(sum_b, off, DNS_WAVE);
-        n += __shfl_xor(n, off, DNS_WAVE);
-    }
-    if ((t & (DNS_WAVE - 1)) == 0) { red[t / DNS_WAVE].a = sum_a; red[t / DNS_WAVE].b = sum_b; red[t / DNS_WAVE].n = n; }
-    __syncthreads();
-    if (t == 0) {
-        sums[0] = (red[0].a + red[1].a) + (red[2].a + red[3].a);
-        sums[1] = (red[0].b + red[1].b) + (red[2].b + red[3].b);
-        count[0] = (int64_t)((red[0].n + red[1].n) + (red[2].n + red[3].n));
+    AgsPartial v;
+    dns_fold_partials<AG_THREADS>(part, n_part, v, red);
+    if (threadIdx.x == 0) {
+        sums[0] = v.a;
+        sums[1] = v.b;
+        count[0] = (int64_t)v.n;
     }
 }
 

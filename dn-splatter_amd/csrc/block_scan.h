@@ -1,8 +1,8 @@
 // block_scan.h — the integer workgroup primitives of the export kernels (pointcloud.hip, levelset.hip, density.hip, metrics.hip,
 // marching.hip): the exclusive scan and the flag rank over the threads of a workgroup, the one-workgroup in-place scan of an array of
 // counts, and the ordered append behind a device cursor that dnsplat_backproject_points and dnsplat_level_points share.  Integers
-// only: the sums are exact in any order, so nothing here is part of a tested bit pattern; the floating-point reductions of the
-// library stay where they are.
+// only: the sums are exact in any order, so nothing here is part of a tested bit pattern; the floating-point folds of the score
+// kernels, whose order is, are in block_reduce.h.
 //
 // THE BARRIER RULE: every helper that takes `wave_tot` opens with the barrier that keeps its writes behind the previous call's
 // reads of the same array.  A call site may therefore sit in a loop, or follow another call on the same array, with no barrier of

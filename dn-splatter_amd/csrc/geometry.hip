@@ -8,19 +8,19 @@
 //                                                d^2 — non-negative doubles order as their patterns, nan patterns above inf — for TWO ranks
 //                                                at once, floor(h) and min(floor(h) + 1, n - 1): LDS histograms added to global ones;
 //                             gm_select_kernel   one workgroup picks the bin of either rank and leaves prefix and remaining rank in scratch;
-//                             gm_finish_kernel   the last pick, the partials added in one fixed order, the square roots, numpy's _lerp and the
-//                                                divisions in double.
+//                             gm_finish_kernel   the last pick, the partials added in the one fixed order of block_reduce.h, the square
+//                                                roots, numpy's _lerp and the divisions in double.
 //   dnsplat_mesh_areas        gm_area_kernel     per triangle: the area in double from the fp32 vertices and the unit face normal.
-//   dnsplat_mesh_sample       gm_sample_kernel   per sample: three words of a counter-based hash of (seed, i) (pc_mix32's family, stated in
+//   dnsplat_mesh_sample       gm_sample_kernel   per sample: three words of a counter-based hash of (seed, i) (dns_mix32's family, stated in
 //                                                dnsplat.h), a binary search in the caller's cdf, a reflected barycentric pair, the point in fp32.
 // No floating-point atomic: the histograms are integers (LDS adds, then 64-bit global adds: order-independent) and the sums are
 // per-workgroup partials folded in a fixed order, so equal inputs give equal bits.  The host reads nothing between the launches: the two
 // ranks and the interpolation weight depend on M and the percentile alone and are kernel arguments.  Compiled without contraction; the
 // two FMAs of d^2 are df_search's own.
 // The hazard of an LDS histogram is the one metrics.hip names: a cloud scored against itself puts every d^2 into ONE bin in every round.
-// gm_hist_add peels the first active lane's bin within the wave once, as mt_hist_add does.
+// dns_hist_add (block_reduce.h) peels the first active lane's bin within the wave once, as it does there.
 
-#include "block_scan.h"
+#include "block_reduce.h"
 #include "density_common.h"
 
 namespace {
@@ -39,6 +39,13 @@ __host__ __device__ constexpr int gm_shift(int round) { return round < 4 ? 53 - 
 struct GmPartial {                                        // 64 bytes
     double sum_d, sum_d2, sum_dot, min_d, max_d;
     long long n_lt, n_le, n_bad;
+    static __device__ GmPartial identity() { return GmPartial{0.0, 0.0, 0.0, INFINITY, -INFINITY, 0, 0, 0}; }
+    __device__ void join(const GmPartial &o)
+    {
+        sum_d += o.sum_d; sum_d2 += o.sum_d2; sum_dot += o.sum_dot;
+        min_d = fmin(min_d, o.min_d); max_d = fmax(max_d, o.max_d);
+        n_lt += o.n_lt; n_le += o.n_le; n_bad += o.n_bad;
+    }
 };
 
 struct GmState {                                          // 64 bytes at the head of the scratch
@@ -80,8 +87,7 @@ __global__ __launch_bounds__(GM_THREADS) void gm_search_kernel(GmSearch a)
     __shared__ GmPartial red[GM_WAVES];
     const int t = threadIdx.x;
     const long long m = (long long)blockIdx.x * GM_THREADS + t;
-    double sum_d = 0.0, sum_d2 = 0.0, sum_dot = 0.0, min_d = INFINITY, max_d = -INFINITY;
-    long long n_lt = 0, n_le = 0, n_bad = 0;
+    GmPartial v = GmPartial::identity();
     if (m < a.M) {
         DfList<1> L;
         const bool ok = df_search<1>(a.ix, a.src[m * 3], a.src[m * 3 + 1], a.src[m * 3 + 2], 1, L);
@@ -92,13 +98,13 @@ __global__ __launch_bounds__(GM_THREADS) void gm_search_kernel(GmSearch a)
         const double d = sqrt(d2);
         a.dist2[m] = d2;
         if (a.idx) a.idx[m] = gi;
-        sum_d = d;
-        sum_d2 = d2;
+        v.sum_d = d;
+        v.sum_d2 = d2;
         if (found) {
-            min_d = max_d = d;
-            n_lt = d < a.threshold;
-            n_le = d <= a.threshold;
-        } else n_bad = 1;
+            v.min_d = v.max_d = d;
+            v.n_lt = d < a.threshold;
+            v.n_le = d <= a.threshold;
+        } else v.n_bad = 1;
         if (a.src_normals) {
             double dot = (double)NAN;
             if (found) {
@@ -115,53 +121,11 @@ __global__ __launch_bounds__(GM_THREADS) void gm_search_kernel(GmSearch a)
                 dot = fabs((g[0] * s[0] + g[1] * s[1]) + g[2] * s[2]);
             }
             if (a.absdot) a.absdot[m] = dot;
-            sum_dot = dot;
+            v.sum_dot = dot;
         }
     }
-#pragma unroll
-    for (int off = DNS_WAVE / 2; off >= 1; off >>= 1) {
-        sum_d += __shfl_xor(sum_d, off, DNS_WAVE);
-        sum_d2 += __shfl_xor(sum_d2, off, DNS_WAVE);
-        sum_dot += __shfl_xor(sum_dot, off, DNS_WAVE);
-        min_d = fmin(min_d, __shfl_xor(min_d, off, DNS_WAVE));
-        max_d = fmax(max_d, __shfl_xor(max_d, off, DNS_WAVE));
-        n_lt += __shfl_xor(n_lt, off, DNS_WAVE);
-        n_le += __shfl_xor(n_le, off, DNS_WAVE);
-        n_bad += __shfl_xor(n_bad, off, DNS_WAVE);
-    }
-    if ((t & (DNS_WAVE - 1)) == 0) {
-        GmPartial &r = red[t / DNS_WAVE];
-        r.sum_d = sum_d; r.sum_d2 = sum_d2; r.sum_dot = sum_dot; r.min_d = min_d; r.max_d = max_d;
-        r.n_lt = n_lt; r.n_le = n_le; r.n_bad = n_bad;
-    }
-    __syncthreads();
-    if (t == 0) {
-        GmPartial p;
-        p.sum_d = (red[0].sum_d + red[1].sum_d) + (red[2].sum_d + red[3].sum_d);
-        p.sum_d2 = (red[0].sum_d2 + red[1].sum_d2) + (red[2].sum_d2 + red[3].sum_d2);
-        p.sum_dot = (red[0].sum_dot + red[1].sum_dot) + (red[2].sum_dot + red[3].sum_dot);
-        p.min_d = fmin(fmin(red[0].min_d, red[1].min_d), fmin(red[2].min_d, red[3].min_d));
-        p.max_d = fmax(fmax(red[0].max_d, red[1].max_d), fmax(red[2].max_d, red[3].max_d));
-        p.n_lt = (red[0].n_lt + red[1].n_lt) + (red[2].n_lt + red[3].n_lt);
-        p.n_le = (red[0].n_le + red[1].n_le) + (red[2].n_le + red[3].n_le);
-        p.n_bad = (red[0].n_bad + red[1].n_bad) + (red[2].n_bad + red[3].n_bad);
-        a.part[blockIdx.x] = p;
-    }
-}
-
-// one count for `bin` from every lane with `active`, into an LDS histogram.  All 64 lanes of the wave call this together.
-__device__ __forceinline__ void gm_hist_add(unsigned int *hist, unsigned int bin, bool active)
-{
-    uint64_t todo = dns_ballot(active);
-    const int lane = threadIdx.x & (DNS_WAVE - 1);
-    if (todo) {                                                                  // wave-uniform
-        const int leader = __builtin_ctzll(todo);
-        const unsigned int b = (unsigned int)__builtin_amdgcn_readlane((int)bin, leader);
-        const uint64_t same = dns_ballot(active && bin == b) & todo;
-        if (lane == leader) atomicAdd(&hist[b], (unsigned int)__builtin_popcountll(same));
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ull) atomicAdd(&hist[bin], 1u);
+    dns_block_join<GM_THREADS>(v, red);
+    if (t == 0) a.part[blockIdx.x] = v;
 }
 
 // round `round`: the d^2 whose upper bits equal the prefix of rank s, counted by their next bits, for both ranks
@@ -182,36 +146,11 @@ __global__ __launch_bounds__(GM_THREADS) void gm_hist_kernel(int round, long lon
         const unsigned long long v = in ? dist2[i] : 0ull;
         const unsigned long long above = round == 0 ? 0ull : v >> (shift + bits);
         const unsigned int bin = (unsigned int)(v >> shift) & ((1u << bits) - 1u);
-        gm_hist_add(hist[0], bin, in && above == prefix0);
-        gm_hist_add(hist[1], bin, in && above == prefix1);
+        dns_hist_add(hist[0], bin, in && above == prefix0);
+        dns_hist_add(hist[1], bin, in && above == prefix1);
     }
     __syncthreads();
-    unsigned long long *global = s.hist + (size_t)round * GM_RANKS * GM_BINS;
-    for (int b = t; b < GM_RANKS * GM_BINS; b += GM_THREADS) {
-        const unsigned int c = (&hist[0][0])[b];
-        if (c) atomicAdd(&global[b], (unsigned long long)c);
-    }
-}
-
-// the bin of hist[0 .. GM_BINS) that holds rank `rank`, by one workgroup: true in the one thread that owns it, with the bin and the rank
-// that remains inside it.  GM_BINS / GM_THREADS consecutive bins per thread, an exclusive scan of the threads' sums.
-__device__ __forceinline__ bool gm_find_bin(const unsigned long long *__restrict__ hist, unsigned long long rank, unsigned long long *wave_sum,
-                                            unsigned int &bin, unsigned long long &rest)
-{
-    constexpr int PER = GM_BINS / GM_THREADS;
-    const int t = threadIdx.x;
-    unsigned long long c[PER], mine = 0ull, all;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { c[k] = hist[t * PER + k]; mine += c[k]; }
-    const unsigned long long before = dns_block_scan<GM_THREADS>(mine, wave_sum, all);
-    if (rank < before || rank >= before + mine) return false;
-    unsigned long long cum = before;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        if (rank < cum + c[k]) { bin = (unsigned int)(t * PER + k); rest = rank - cum; return true; }
-        cum += c[k];
-    }
-    return false;
+    dns_hist_flush<GM_THREADS>(&hist[0][0], s.hist + (size_t)round * GM_RANKS * GM_BINS, GM_RANKS * GM_BINS);
 }
 
 // round 0 starts from the two ranks the host derived from (M, percentile); the later rounds from what the round before left
@@ -227,10 +166,10 @@ __global__ __launch_bounds__(GM_THREADS) void gm_select_kernel(int round, unsign
     }
     __syncthreads();                                                             // every thread has read the state before one rewrites it
 #pragma unroll
-    for (int r = 0; r < GM_RANKS; ++r) {
+    for (int r = 0; r < GM_RANKS; ++r) {                                         // wave_sum twice: dns_block_scan's barrier rule
         unsigned int bin;
         unsigned long long rest;
-        if (gm_find_bin(s.hist + ((size_t)round * GM_RANKS + r) * GM_BINS, rank[r], wave_sum, bin, rest)) {
+        if (dns_find_bin<GM_THREADS, GM_BINS>(s.hist + ((size_t)round * GM_RANKS + r) * GM_BINS, rank[r], wave_sum, bin, rest)) {
             s.state->rank[r] = rest;
             s.state->prefix[r] = (prefix[r] << gm_bits(round)) | bin;
         }
@@ -248,70 +187,39 @@ __global__ __launch_bounds__(GM_THREADS) void gm_finish_kernel(long long M, int 
     if (t < GM_RANKS) order_bits[t] = 0x7ff8000000000000ull;
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < GM_RANKS; ++r) {
+    for (int r = 0; r < GM_RANKS; ++r) {                                         // wave_sum twice: dns_block_scan's barrier rule
         unsigned int bin;
         unsigned long long rest;
-        if (gm_find_bin(s.hist + ((size_t)(GM_ROUNDS - 1) * GM_RANKS + r) * GM_BINS, s.state->rank[r], wave_sum, bin, rest))
+        if (dns_find_bin<GM_THREADS, GM_BINS>(s.hist + ((size_t)(GM_ROUNDS - 1) * GM_RANKS + r) * GM_BINS, s.state->rank[r], wave_sum, bin, rest))
             order_bits[r] = (s.state->prefix[r] << gm_bits(GM_ROUNDS - 1)) | bin;
     }
 
-    double sum_d = 0.0, sum_d2 = 0.0, sum_dot = 0.0, min_d = INFINITY, max_d = -INFINITY;
-    long long n_lt = 0, n_le = 0, n_bad = 0;
-    for (int i = t; i < n_part; i += GM_THREADS) {
-        const GmPartial p = s.part[i];
-        sum_d += p.sum_d; sum_d2 += p.sum_d2; sum_dot += p.sum_dot;
-        min_d = fmin(min_d, p.min_d); max_d = fmax(max_d, p.max_d);
-        n_lt += p.n_lt; n_le += p.n_le; n_bad += p.n_bad;
-    }
-#pragma unroll
-    for (int off = DNS_WAVE / 2; off >= 1; off >>= 1) {
-        sum_d += __shfl_xor(sum_d, off, DNS_WAVE);
-        sum_d2 += __shfl_xor(sum_d2, off, DNS_WAVE);
-        sum_dot += __shfl_xor(sum_dot, off, DNS_WAVE);
-        min_d = fmin(min_d, __shfl_xor(min_d, off, DNS_WAVE));
-        max_d = fmax(max_d, __shfl_xor(max_d, off, DNS_WAVE));
-        n_lt += __shfl_xor(n_lt, off, DNS_WAVE);
-        n_le += __shfl_xor(n_le, off, DNS_WAVE);
-        n_bad += __shfl_xor(n_bad, off, DNS_WAVE);
-    }
-    if ((t & (DNS_WAVE - 1)) == 0) {
-        GmPartial &r = red[t / DNS_WAVE];
-        r.sum_d = sum_d; r.sum_d2 = sum_d2; r.sum_dot = sum_dot; r.min_d = min_d; r.max_d = max_d;
-        r.n_lt = n_lt; r.n_le = n_le; r.n_bad = n_bad;
-    }
-    __syncthreads();                                                             // also: order_bits is written
+    GmPartial v;
+    dns_fold_partials<GM_THREADS>(s.part, n_part, v, red);                       // its barriers also publish order_bits
     if (t != 0) return;
-    sum_d = (red[0].sum_d + red[1].sum_d) + (red[2].sum_d + red[3].sum_d);
-    sum_d2 = (red[0].sum_d2 + red[1].sum_d2) + (red[2].sum_d2 + red[3].sum_d2);
-    sum_dot = (red[0].sum_dot + red[1].sum_dot) + (red[2].sum_dot + red[3].sum_dot);
-    min_d = fmin(fmin(red[0].min_d, red[1].min_d), fmin(red[2].min_d, red[3].min_d));
-    max_d = fmax(fmax(red[0].max_d, red[1].max_d), fmax(red[2].max_d, red[3].max_d));
-    n_lt = (red[0].n_lt + red[1].n_lt) + (red[2].n_lt + red[3].n_lt);
-    n_le = (red[0].n_le + red[1].n_le) + (red[2].n_le + red[3].n_le);
-    n_bad = (red[0].n_bad + red[1].n_bad) + (red[2].n_bad + red[3].n_bad);
 
     const double nan_ = __longlong_as_double(0x7ff8000000000000ll);
     const double n = (double)M;
-    const bool bad = n_bad > 0;                                                  // numpy: a nan among the distances makes all of these nan
+    const bool bad = v.n_bad > 0;                                                // numpy: a nan among the distances makes all of these nan
     const double lo2 = __longlong_as_double((long long)order_bits[0]), hi2 = __longlong_as_double((long long)order_bits[1]);
     const double lo = sqrt(lo2), hi = sqrt(hi2);
     const double diff = hi - lo;                                                 // numpy's _lerp
     const double lerp = weight >= 0.5 ? hi - diff * (1.0 - weight) : lo + diff * weight;
     for (int k = 0; k < DNSPLAT_GEOM_COUNT; ++k) scalars[k] = 0.0;
-    scalars[DNSPLAT_GEOM_MEAN_D] = sum_d / n;                                    // a nan row has added its nan
-    scalars[DNSPLAT_GEOM_MEAN_D2] = sum_d2 / n;
-    scalars[DNSPLAT_GEOM_MEAN_ABSDOT] = has_normals ? sum_dot / n : nan_;
+    scalars[DNSPLAT_GEOM_MEAN_D] = v.sum_d / n;                                  // a nan row has added its nan
+    scalars[DNSPLAT_GEOM_MEAN_D2] = v.sum_d2 / n;
+    scalars[DNSPLAT_GEOM_MEAN_ABSDOT] = has_normals ? v.sum_dot / n : nan_;
     scalars[DNSPLAT_GEOM_PERCENTILE] = bad ? nan_ : lerp;
-    scalars[DNSPLAT_GEOM_SHARE_LT] = (double)n_lt / n;
-    scalars[DNSPLAT_GEOM_SHARE_LE] = (double)n_le / n;
-    scalars[DNSPLAT_GEOM_MIN_D] = bad ? nan_ : min_d;
-    scalars[DNSPLAT_GEOM_MAX_D] = bad ? nan_ : max_d;
+    scalars[DNSPLAT_GEOM_SHARE_LT] = (double)v.n_lt / n;
+    scalars[DNSPLAT_GEOM_SHARE_LE] = (double)v.n_le / n;
+    scalars[DNSPLAT_GEOM_MIN_D] = bad ? nan_ : v.min_d;
+    scalars[DNSPLAT_GEOM_MAX_D] = bad ? nan_ : v.max_d;
     scalars[DNSPLAT_GEOM_ORDER_LO_D2] = lo2;
     scalars[DNSPLAT_GEOM_ORDER_HI_D2] = hi2;
     counts[DNSPLAT_GEOM_N] = (int64_t)M;
-    counts[DNSPLAT_GEOM_N_LT] = (int64_t)n_lt;
-    counts[DNSPLAT_GEOM_N_LE] = (int64_t)n_le;
-    counts[DNSPLAT_GEOM_N_NONFINITE] = (int64_t)n_bad;
+    counts[DNSPLAT_GEOM_N_LT] = (int64_t)v.n_lt;
+    counts[DNSPLAT_GEOM_N_LE] = (int64_t)v.n_le;
+    counts[DNSPLAT_GEOM_N_NONFINITE] = (int64_t)v.n_bad;
 }
 
 // ---- the mesh sampler ----------------------------------------------------------------------------------------------------------------
@@ -344,15 +252,6 @@ __global__ __launch_bounds__(GM_THREADS) void gm_area_kernel(int V, int T, const
     normals[f * 3] = n[0]; normals[f * 3 + 1] = n[1]; normals[f * 3 + 2] = n[2];
 }
 
-// pc_mix32 of pointcloud.hip (the "lowbias32" finaliser): the same family of integer hashes as the pixel sampler's
-__device__ __forceinline__ uint32_t gm_mix32(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 struct GmSample {
     long long S;
     uint32_t key;
@@ -368,8 +267,8 @@ __global__ __launch_bounds__(GM_THREADS) void gm_sample_kernel(GmSample a)
 {
     const long long i = (long long)blockIdx.x * GM_THREADS + threadIdx.x;
     if (i >= a.S) return;
-    const uint32_t c = gm_mix32((uint32_t)i ^ a.key);
-    const uint32_t w0 = gm_mix32(c + 0x9e3779b9u), w1 = gm_mix32(c + 2u * 0x9e3779b9u), w2 = gm_mix32(c + 3u * 0x9e3779b9u);
+    const uint32_t c = dns_mix32((uint32_t)i ^ a.key);
+    const uint32_t w0 = dns_mix32(c + 0x9e3779b9u), w1 = dns_mix32(c + 2u * 0x9e3779b9u), w2 = dns_mix32(c + 3u * 0x9e3779b9u);
     const double total = a.cdf[a.T - 1];
     const float nanf_ = __uint_as_float(0x7fc00000u);
     float p[3] = {nanf_, nanf_, nanf_}, n[3] = {0.f, 0.f, 0.f};
@@ -471,11 +370,7 @@ extern "C" int dnsplat_mesh_sample(const dnsplat_mesh_sample_args *a, dnsplat_st
     GmSample q;
     q.S = a->S;
     // the key of the draw: both halves of the seed through the hash, as pc_permute keys its rounds
-    uint32_t x = (uint32_t)(a->seed >> 32) + 0x9e3779b9u;
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    x ^= (uint32_t)a->seed;
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    q.key = x;
+    q.key = dns_mix32((uint32_t)a->seed ^ dns_mix32((uint32_t)(a->seed >> 32) + 0x9e3779b9u));
     q.T = a->T; q.V = a->V;
     q.cdf = a->cdf; q.vertices = a->vertices; q.face_normals = a->face_normals; q.triangles = a->triangles;
     q.points = a->points; q.normals = a->normals; q.faces = a->faces;

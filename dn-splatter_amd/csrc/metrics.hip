@@ -12,21 +12,21 @@
 //   mt_select_kernel   one workgroup finds the bin that holds the wanted rank and leaves prefix and remaining rank in scratch;
 //   mt_hist_kernel     rounds two (11 bits) and three (9 bits) re-read the two normal images as flat arrays (float4 where both are
 //                      16-byte aligned) and count only the elements whose prefix matches;
-//   mt_finish_kernel   the last selection, the partials added in one fixed order, the divisions, square roots and log10 in double,
-//                      rounded once to fp32.
+//   mt_finish_kernel   the last selection, the partials added in the one fixed order of block_reduce.h (dns_fold_partials), the
+//                      divisions, square roots and log10 in double, rounded once to fp32.
 // The host reads nothing between the launches.  No floating-point atomic: the histograms are integers (LDS adds, then 64-bit global
 // adds: order-independent), the sums are per-workgroup partials folded in a fixed order: equal inputs give equal bits.
 // Non-negative floats order as their bit patterns, nan patterns above inf; torch.median returns nan if any value is nan, which is the
 // count of nan differences here.  The decisions (gt > tolerance, t < 1.25^k, the bits of |g - p|) are single correctly rounded fp32
 // operations, compiled without contraction: they are torch's, bit for bit.
 // The hazard of an LDS histogram: on real images almost all of |g - p| falls into a few dozen of round one's bins, on identical images
-// into ONE, and 64 lanes adding to one LDS word serialise.  mt_hist_add peels equal bins within the wave first (the first active
-// lane's bin, one add of the ballot's population count), MT_PEEL times; what is left after that is spread and adds per lane.  Measured
+// into ONE, and 64 lanes adding to one LDS word serialise.  dns_hist_add<MT_PEEL> (block_reduce.h) peels equal bins within the wave
+// first (the first active lane's bin, one add of the ballot's population count), MT_PEEL times; what is left adds per lane.  Measured
 // at 1600 x 1200 (docs/history.md, section 15): one peel costs 3 % on random images and covers the one-bin case; peeling until
 // nothing is left (up to 64 rounds on random images) doubles the call.
 // Traffic: 56 B per pixel read once, plus 24 B per pixel for each of rounds two and three.
 
-#include "block_scan.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -36,7 +36,6 @@ constexpr int MT_PER = 4;                                // pixels per thread of
 constexpr int MT_SPAN = MT_THREADS * MT_PER;             // pixels per workgroup of the sweep
 constexpr int MT_HPER = 16;                              // elements per thread of rounds two and three
 constexpr int MT_HSPAN = MT_THREADS * MT_HPER;           // elements per workgroup there
-constexpr int MT_FOLD = MT_THREADS;                      // partials the finish kernel takes per trip
 constexpr int MT_BITS1 = 11, MT_BITS2 = 11, MT_BITS3 = 9;
 constexpr int MT_BINS1 = 1 << MT_BITS1, MT_BINS2 = 1 << MT_BITS2, MT_BINS3 = 1 << MT_BITS3;
 #ifndef MT_PEEL
@@ -47,6 +46,14 @@ constexpr int MT_ND = 8, MT_NI = 6;                      // sums and counts of a
 struct MtPartial {                                       // 112 bytes
     double d[MT_ND];                                     // DNSPLAT_METRIC_SUM_* order
     long long i[MT_NI];                                  // masked, a1, a2, a3, non-nan log terms, nan normal differences
+    static __device__ MtPartial identity() { return MtPartial{}; }
+    __device__ void join(const MtPartial &o)
+    {
+#pragma unroll
+        for (int k = 0; k < MT_ND; ++k) d[k] += o.d[k];
+#pragma unroll
+        for (int k = 0; k < MT_NI; ++k) i[k] += o.i[k];
+    }
 };
 
 struct MtState {                                         // 64 bytes at the head of the scratch
@@ -74,31 +81,6 @@ __host__ __device__ inline MtScratch mt_carve(void *scratch)
 }
 
 constexpr size_t MT_HEAD_BYTES = sizeof(MtState) + sizeof(unsigned long long) * (MT_BINS1 + MT_BINS2 + MT_BINS3);
-
-// one count for `bin` from every lane with `active`, into an LDS histogram.  All 64 lanes of the wave call this together.
-__device__ __forceinline__ void mt_hist_add(unsigned int *hist, unsigned int bin, bool active)
-{
-    uint64_t todo = dns_ballot(active);
-    const int lane = threadIdx.x & (DNS_WAVE - 1);
-    for (int k = 0; k < MT_PEEL && todo; ++k) {                                   // wave-uniform: todo lives in scalar registers
-        const int leader = __builtin_ctzll(todo);
-        const unsigned int b = (unsigned int)__builtin_amdgcn_readlane((int)bin, leader);
-        const uint64_t same = dns_ballot(active && bin == b) & todo;
-        if (lane == leader) atomicAdd(&hist[b], (unsigned int)__builtin_popcountll(same));
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ull) atomicAdd(&hist[bin], 1u);
-}
-
-// the LDS histogram of a workgroup, added to the global one (64-bit: a frame holds up to 3 (2^31 - 1) elements)
-template <int BINS>
-__device__ __forceinline__ void mt_flush(const unsigned int *hist, unsigned long long *global)
-{
-    for (int b = threadIdx.x; b < BINS; b += MT_THREADS) {
-        const unsigned int c = hist[b];
-        if (c) atomicAdd(&global[b], (unsigned long long)c);
-    }
-}
 
 __global__ __launch_bounds__(MT_THREADS) void mt_zero_kernel(unsigned long long n, void *scratch)
 {
@@ -185,11 +167,13 @@ __global__ __launch_bounds__(MT_THREADS) void mt_sweep_kernel(long long P, const
                     d[DNSPLAT_METRIC_SUM_NORMAL_ABS] += (double)e;
                     n[5] += v > 0x7f800000u;
                 }
-                mt_hist_add(hist, v >> (MT_BITS2 + MT_BITS3), in);
+                dns_hist_add<MT_PEEL>(hist, v >> (MT_BITS2 + MT_BITS3), in);
             }
         }
     }
 
+    // dns_block_join's order, written out field by field: with the fourteen fields in one struct this kernel, which sits exactly at
+    // 64 VGPRs, needs 71 to 80 and loses up to two waves per SIMD (docs/history.md, section 24)
 #pragma unroll
     for (int off = DNS_WAVE / 2; off >= 1; off >>= 1) {
 #pragma unroll
@@ -209,7 +193,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_sweep_kernel(long long P, const
         const int k = t - MT_ND;
         s.part[blockIdx.x].i[k] = (red[0].i[k] + red[1].i[k]) + (red[2].i[k] + red[3].i[k]);
     }
-    if (normal) mt_flush<MT_BINS1>(hist, s.hist1);
+    if (normal) dns_hist_flush<MT_THREADS>(hist, s.hist1, MT_BINS1);
 }
 
 // rounds two and three: the elements of |g - p| whose upper bits equal the prefix found so far, counted by their next BITS bits.  The two
@@ -230,7 +214,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_hist_kernel(unsigned long long 
     const unsigned int prefix = s.state->prefix;
     auto count = [&](float g, float q, bool in) {
         const unsigned int v = __float_as_uint(fabsf(__fsub_rn(g, q))) & 0x7fffffffu;
-        mt_hist_add(hist, (v >> SHIFT) & (BINS - 1), in && (v >> (SHIFT + BITS)) == prefix);
+        dns_hist_add<MT_PEEL>(hist, (v >> SHIFT) & (BINS - 1), in && (v >> (SHIFT + BITS)) == prefix);
     };
     if constexpr (VEC) {
         const unsigned long long n4 = n / 4ull;
@@ -268,42 +252,20 @@ __global__ __launch_bounds__(MT_THREADS) void mt_hist_kernel(unsigned long long 
         }
     }
     __syncthreads();
-    mt_flush<BINS>(hist, ROUND == 2 ? s.hist2 : s.hist3);
-}
-
-// the bin of `hist` that holds rank `rank`, by one workgroup: returns true in the one thread that owns it, with the bin and the rank
-// that remains inside it.  BINS / MT_THREADS consecutive bins per thread, an exclusive scan of the threads' sums.
-template <int BINS>
-__device__ __forceinline__ bool mt_find_bin(const unsigned long long *__restrict__ hist, unsigned long long rank, unsigned int &bin,
-                                            unsigned long long &rest)
-{
-    constexpr int PER = BINS / MT_THREADS;
-    __shared__ unsigned long long wave_sum[MT_WAVES];
-    const int t = threadIdx.x;
-    unsigned long long c[PER], mine = 0ull, all;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { c[k] = hist[t * PER + k]; mine += c[k]; }
-    const unsigned long long before = dns_block_scan<MT_THREADS>(mine, wave_sum, all);
-    if (rank < before || rank >= before + mine) return false;
-    unsigned long long cum = before;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        if (rank < cum + c[k]) { bin = (unsigned int)(t * PER + k); rest = rank - cum; return true; }
-        cum += c[k];
-    }
-    return false;
+    dns_hist_flush<MT_THREADS>(hist, ROUND == 2 ? s.hist2 : s.hist3, BINS);
 }
 
 template <int ROUND>
 __global__ __launch_bounds__(MT_THREADS) void mt_select_kernel(void *scratch)
 {
+    __shared__ unsigned long long wave_sum[MT_WAVES];
     const MtScratch s = mt_carve(scratch);
     const unsigned long long rank = s.state->rank;
     const unsigned int prefix = s.state->prefix;
     __syncthreads();                                                             // every thread has read the state before one rewrites it
     unsigned int bin;
     unsigned long long rest;
-    if (mt_find_bin<(ROUND == 1 ? MT_BINS1 : MT_BINS2)>(ROUND == 1 ? s.hist1 : s.hist2, rank, bin, rest)) {
+    if (dns_find_bin<MT_THREADS, (ROUND == 1 ? MT_BINS1 : MT_BINS2)>(ROUND == 1 ? s.hist1 : s.hist2, rank, wave_sum, bin, rest)) {
         s.state->rank = rest;
         s.state->prefix = (prefix << (ROUND == 1 ? MT_BITS1 : MT_BITS2)) | bin;
     }
@@ -314,6 +276,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_finish_kernel(long long P, int 
                                                                 double *__restrict__ sums)
 {
     __shared__ MtPartial red[MT_WAVES];
+    __shared__ unsigned long long wave_sum[MT_WAVES];
     __shared__ unsigned int median_bits;
     const MtScratch s = mt_carve(scratch);
     const int t = threadIdx.x;
@@ -322,40 +285,14 @@ __global__ __launch_bounds__(MT_THREADS) void mt_finish_kernel(long long P, int 
     if (has_normal) {
         unsigned int bin;
         unsigned long long rest;
-        if (mt_find_bin<MT_BINS3>(s.hist3, s.state->rank, bin, rest)) median_bits = (s.state->prefix << MT_BITS3) | bin;
+        if (dns_find_bin<MT_THREADS, MT_BINS3>(s.hist3, s.state->rank, wave_sum, bin, rest)) median_bits = (s.state->prefix << MT_BITS3) | bin;
     }
 
-    double d[MT_ND];
-    long long n[MT_NI];
-#pragma unroll
-    for (int k = 0; k < MT_ND; ++k) d[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < MT_NI; ++k) n[k] = 0;
-    for (int i = t; i < n_part; i += MT_FOLD) {
-#pragma unroll
-        for (int k = 0; k < MT_ND; ++k) d[k] += s.part[i].d[k];
-#pragma unroll
-        for (int k = 0; k < MT_NI; ++k) n[k] += s.part[i].i[k];
-    }
-#pragma unroll
-    for (int off = DNS_WAVE / 2; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < MT_ND; ++k) d[k] += __shfl_xor(d[k], off, DNS_WAVE);
-#pragma unroll
-        for (int k = 0; k < MT_NI; ++k) n[k] += __shfl_xor(n[k], off, DNS_WAVE);
-    }
-    if ((t & (DNS_WAVE - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < MT_ND; ++k) red[t / DNS_WAVE].d[k] = d[k];
-#pragma unroll
-        for (int k = 0; k < MT_NI; ++k) red[t / DNS_WAVE].i[k] = n[k];
-    }
-    __syncthreads();
+    MtPartial v;
+    dns_fold_partials<MT_THREADS>(s.part, n_part, v, red);                       // its barriers also publish median_bits
     if (t != 0) return;
-#pragma unroll
-    for (int k = 0; k < MT_ND; ++k) d[k] = (red[0].d[k] + red[1].d[k]) + (red[2].d[k] + red[3].d[k]);
-#pragma unroll
-    for (int k = 0; k < MT_NI; ++k) n[k] = (red[0].i[k] + red[1].i[k]) + (red[2].i[k] + red[3].i[k]);
+    const double (&d)[MT_ND] = v.d;
+    const long long (&n)[MT_NI] = v.i;
 
     const float nanf_ = __uint_as_float(0x7fc00000u);
     for (int k = 0; k < DNSPLAT_METRIC_COUNT; ++k) metrics[k] = k < DNSPLAT_METRIC_USED ? nanf_ : 0.f;   // an absent pair: nan

@@ -11,11 +11,11 @@
 //   pearson_grad_kernel                           one thread per pixel: within a region the gradient is affine in the pixel's own two
 //                                                 values, d loss / d p_j = alpha b_j + beta a_j, so a thread walks the region table
 //                                                 (staged through LDS in pieces) and adds the regions that hold its pixel, in table order.
-// Sums and coefficients are kept in double (a few adds per pixel beside two loads: the kernels are memory-bound), every reduction is a
-// fixed tree and there is no atomic: equal inputs give equal bits.  Raw one-pass fp32 moments lose the variance of a low-contrast
-// frame (5 + 0.01 u over 1600 x 1200: 8 % off), hence two sweeps.
+// Sums and coefficients are kept in double (a few adds per pixel beside two loads: the kernels are memory-bound), every reduction is the
+// fixed tree of block_reduce.h (dns_block_join, dns_fold_partials) and there is no atomic: equal inputs give equal bits.  Raw one-pass
+// fp32 moments lose the variance of a low-contrast frame (5 + 0.01 u over 1600 x 1200: 8 % off), hence two sweeps.
 
-#include "splat_common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -31,25 +31,17 @@ struct PearsonRegion {                   // 48 bytes
     int32_t row0, col0;
 };
 
+struct PsSums {                          // 24 bytes: three sums of one sweep, reduced together
+    double v[3];
+    static __device__ PsSums identity() { return PsSums{{0.0, 0.0, 0.0}}; }
+    __device__ void join(const PsSums &o) { v[0] += o.v[0]; v[1] += o.v[1]; v[2] += o.v[2]; }
+};
+
 struct PearsonScratch {                  // layout of the caller's scratch (dnsplat_pearson_scratch_bytes)
-    double *part1, *part2;               // [PS_FRAME_BLOCKS][3] each
+    double *part1, *part2;               // [PS_FRAME_BLOCKS][3] each: the kernels read and write them as PsSums
     PearsonRegion *frame;                // [1]
     PearsonRegion *boxes;                // [n_boxes]
 };
-
-__device__ __forceinline__ void block_sum3(double v[3], double (*red)[3])
-{
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[q] += __shfl_xor(v[q], off, DNS_WAVE);
-    const int w = threadIdx.x / DNS_WAVE;
-    __syncthreads();
-    if ((threadIdx.x & (DNS_WAVE - 1)) == 0) { red[w][0] = v[0]; red[w][1] = v[1]; red[w][2] = v[2]; }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 3; ++q) v[q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
-}
 
 // mean-centred moments -> what the gradient pass needs.  n < 2: 0 / 0, nan as the reference's std of one element.  s_p == 0 (a
 // constant prediction): the value is 1 - 0; autograd's std backward sends no gradient through a standard deviation of exactly zero,
@@ -71,38 +63,32 @@ __device__ __forceinline__ void pearson_coefficients(double n, double mu_p, doub
 __global__ __launch_bounds__(PS_THREADS) void pearson_frame_sums_kernel(long long P, const float *__restrict__ pred, const float *__restrict__ gt,
                                                                          const uint8_t *__restrict__ mask, double *__restrict__ part1)
 {
-    __shared__ double red[4][3];
-    double v[3] = {0.0, 0.0, 0.0};
+    __shared__ PsSums red[PS_THREADS / DNS_WAVE];
+    PsSums acc = PsSums::identity();
+    double (&v)[3] = acc.v;
     for (long long px = (long long)blockIdx.x * PS_THREADS + threadIdx.x; px < P; px += (long long)gridDim.x * PS_THREADS)
         if (!mask || mask[px]) { v[0] += 1.0; v[1] += (double)pred[px]; v[2] += (double)gt[px]; }
-    block_sum3(v, red);
-    if (threadIdx.x == 0) { part1[3 * blockIdx.x] = v[0]; part1[3 * blockIdx.x + 1] = v[1]; part1[3 * blockIdx.x + 2] = v[2]; }
-}
-
-// the partials of all workgroups, added in one fixed order (every caller gets the same bits)
-__device__ __forceinline__ void fold_partials(const double *__restrict__ part, int n_part, double v[3], double (*red)[3])
-{
-    v[0] = v[1] = v[2] = 0.0;
-    for (int i = threadIdx.x; i < n_part; i += PS_THREADS) { v[0] += part[3 * i]; v[1] += part[3 * i + 1]; v[2] += part[3 * i + 2]; }
-    block_sum3(v, red);
+    dns_block_join<PS_THREADS>(acc, red);
+    if (threadIdx.x == 0) ((PsSums *)part1)[blockIdx.x] = acc;
 }
 
 __global__ __launch_bounds__(PS_THREADS) void pearson_frame_moments_kernel(long long P, const float *__restrict__ pred, const float *__restrict__ gt,
                                                                             const uint8_t *__restrict__ mask, const double *__restrict__ part1,
                                                                             double *__restrict__ part2)
 {
-    __shared__ double red[4][3];
-    double s[3];
-    fold_partials(part1, gridDim.x, s, red);
-    const double mu_p = s[1] / s[0], mu_t = s[2] / s[0];
-    double v[3] = {0.0, 0.0, 0.0};
+    __shared__ PsSums red[PS_THREADS / DNS_WAVE];
+    PsSums acc;
+    dns_fold_partials<PS_THREADS>((const PsSums *)part1, gridDim.x, acc, red);   // every workgroup gets the same bits
+    double (&v)[3] = acc.v;
+    const double mu_p = v[1] / v[0], mu_t = v[2] / v[0];
+    acc = PsSums::identity();
     for (long long px = (long long)blockIdx.x * PS_THREADS + threadIdx.x; px < P; px += (long long)gridDim.x * PS_THREADS)
         if (!mask || mask[px]) {
             const double a = (double)pred[px] - mu_p, b = (double)gt[px] - mu_t;
             v[0] += a * a; v[1] += b * b; v[2] += a * b;
         }
-    block_sum3(v, red);
-    if (threadIdx.x == 0) { part2[3 * blockIdx.x] = v[0]; part2[3 * blockIdx.x + 1] = v[1]; part2[3 * blockIdx.x + 2] = v[2]; }
+    dns_block_join<PS_THREADS>(acc, red);
+    if (threadIdx.x == 0) ((PsSums *)part2)[blockIdx.x] = acc;
 }
 
 // One workgroup per box.  REG: the box is at most PS_REG_PIXELS pixels per lane and stays in registers between the two sweeps;
@@ -112,13 +98,14 @@ __global__ __launch_bounds__(PS_THREADS) void pearson_box_kernel(int W, int H, i
                                                                   const int64_t *__restrict__ rows, const int64_t *__restrict__ cols,
                                                                   PearsonRegion *__restrict__ regions)
 {
-    __shared__ double red[4][3];
+    __shared__ PsSums red[PS_THREADS / DNS_WAVE];
     const long long r64 = rows[blockIdx.x], c64 = cols[blockIdx.x];
     const int row0 = (int)(r64 < 0 ? 0 : (r64 > H - box ? H - box : r64)), col0 = (int)(c64 < 0 ? 0 : (c64 > W - box ? W - box : c64));
     const int n = box * box;                                  // box <= 46340 is checked at launch
     const size_t base = (size_t)row0 * W + col0;
     float p[REG ? PS_REG_PIXELS : 1], t[REG ? PS_REG_PIXELS : 1];
-    double v[3] = {0.0, 0.0, 0.0};
+    PsSums acc = PsSums::identity();
+    double (&v)[3] = acc.v;
     if (REG) {
 #pragma unroll
         for (int k = 0; k < PS_REG_PIXELS; ++k) {
@@ -139,9 +126,9 @@ __global__ __launch_bounds__(PS_THREADS) void pearson_box_kernel(int W, int H, i
             v[1] += (double)pred[px]; v[2] += (double)gt[px];
         }
     }
-    block_sum3(v, red);
+    dns_block_join<PS_THREADS>(acc, red);
     const double mu_p = v[1] / (double)n, mu_t = v[2] / (double)n;
-    v[0] = v[1] = v[2] = 0.0;
+    acc = PsSums::identity();
     if (REG) {
 #pragma unroll
         for (int k = 0; k < PS_REG_PIXELS; ++k)
@@ -157,7 +144,7 @@ __global__ __launch_bounds__(PS_THREADS) void pearson_box_kernel(int W, int H, i
             v[0] += a * a; v[1] += b * b; v[2] += a * b;
         }
     }
-    block_sum3(v, red);
+    dns_block_join<PS_THREADS>(acc, red);
     if (threadIdx.x == 0) pearson_coefficients((double)n, mu_p, mu_t, v[0], v[1], v[2], row0, col0, regions + blockIdx.x);
 }
 
@@ -166,22 +153,22 @@ __global__ __launch_bounds__(PS_THREADS) void pearson_finish_kernel(int whole, i
                                                                      PearsonRegion *__restrict__ frame, int n_boxes,
                                                                      const PearsonRegion *__restrict__ boxes, float *__restrict__ sums)
 {
-    __shared__ double red[4][3];
-    double s1[3], s2[3];
+    __shared__ PsSums red[PS_THREADS / DNS_WAVE];
     if (whole) {
-        fold_partials(part1, n_part, s1, red);
-        fold_partials(part2, n_part, s2, red);
+        PsSums s1, s2;
+        dns_fold_partials<PS_THREADS>((const PsSums *)part1, n_part, s1, red);
+        dns_fold_partials<PS_THREADS>((const PsSums *)part2, n_part, s2, red);
         if (threadIdx.x == 0) {
-            pearson_coefficients(s1[0], s1[1] / s1[0], s1[2] / s1[0], s2[0], s2[1], s2[2], 0, 0, frame);
+            pearson_coefficients(s1.v[0], s1.v[1] / s1.v[0], s1.v[2] / s1.v[0], s2.v[0], s2.v[1], s2.v[2], 0, 0, frame);
             sums[0] = (float)frame->loss;
         }
     } else if (threadIdx.x == 0) {
         sums[0] = 0.f;
     }
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < n_boxes; i += PS_THREADS) v[0] += boxes[i].loss;
-    block_sum3(v, red);
-    if (threadIdx.x == 0) sums[1] = (float)v[0];
+    PsSums acc = PsSums::identity();
+    for (int i = threadIdx.x; i < n_boxes; i += PS_THREADS) acc.v[0] += boxes[i].loss;
+    dns_block_join<PS_THREADS>(acc, red);
+    if (threadIdx.x == 0) sums[1] = (float)acc.v[0];
 }
 
 __global__ __launch_bounds__(PS_THREADS) void pearson_grad_kernel(int W, int H, int box, const float *__restrict__ pred, const float *__restrict__ gt,

@@ -17,7 +17,7 @@
 // No atomic anywhere and no sum whose order depends on scheduling: equal inputs (and seed) give equal bits.  Compiled without
 // contraction: every product and sum below is the single fp32 operation torch performs.
 
-#include "block_scan.h"
+#include "block_reduce.h"
 #include "pixel_camera.h"
 
 namespace {
@@ -124,15 +124,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_edge_dilate_kernel(int W, int H
 
 // ---- the sampler ---------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t pc_mix32(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// the keyed bijection of [0, n) that dnsplat.h states
+// the keyed bijection of [0, n) that dnsplat.h states, on dns_mix32 (block_reduce.h)
 __device__ __forceinline__ uint32_t pc_permute(uint32_t t, uint32_t n, uint64_t seed)
 {
     const int bits = n > 1u ? 32 - __clz(n - 1u) : 0;
@@ -141,13 +133,13 @@ __device__ __forceinline__ uint32_t pc_permute(uint32_t t, uint32_t n, uint64_t 
     uint32_t key[DNSPLAT_SAMPLE_ROUNDS];
 #pragma unroll
     for (int r = 0; r < DNSPLAT_SAMPLE_ROUNDS; ++r)
-        key[r] = pc_mix32((uint32_t)seed ^ pc_mix32((uint32_t)(seed >> 32) + 0x9e3779b9u * (uint32_t)(r + 1)));
+        key[r] = dns_mix32((uint32_t)seed ^ dns_mix32((uint32_t)(seed >> 32) + 0x9e3779b9u * (uint32_t)(r + 1)));
     uint32_t x = t;
     do {
         uint32_t L = x >> half, R = x & mask;
 #pragma unroll
         for (int r = 0; r < DNSPLAT_SAMPLE_ROUNDS; ++r) {
-            const uint32_t f = pc_mix32(R ^ key[r]) & mask;
+            const uint32_t f = dns_mix32(R ^ key[r]) & mask;
             const uint32_t nr = L ^ f;
             L = R;
             R = nr;

@@ -215,7 +215,7 @@ _GOLDEN = 0x9E3779B9
 
 
 def mix32(x: Tensor) -> Tensor:
-    """``pc_mix32`` on int64 tensors that hold uint32 values."""
+    """``dns_mix32`` (csrc/block_reduce.h) on int64 tensors that hold uint32 values."""
     x = x ^ (x >> 16)
     x = (x * 0x7FEB352D) & _M32
     x = x ^ (x >> 15)

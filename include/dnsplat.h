@@ -924,7 +924,7 @@ int dnsplat_mc_emit(const dnsplat_mc_args *args, dnsplat_stream_t stream);
  *   bounds.  One launch.  The inclusive prefix sum of the areas is the caller's (any double scan; the Python layer uses torch.cumsum).
  *
  * dnsplat_mesh_sample — mesh.sample(count, return_index=True) as a canonical function of (mesh, cdf, seed).  Sample i of S, one thread:
- *   words      mix(x) = pc_mix32 of the pixel sampler (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16).
+ *   words      mix(x) = the mix32 of the pixel sampler (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16).
  *              key = mix((uint32)seed ^ mix((uint32)(seed >> 32) + 0x9e3779b9)); c = mix((uint32)i ^ key);
  *              w_k = mix(c + (k + 1) 0x9e3779b9), k = 0, 1, 2 (uint32 arithmetic): a counter-based integer hash, no state.
  *   face       t = ((double)w_0 + 0.5) / 2^32 * cdf[T - 1]; f = the first index with cdf[f] > t (binary search).  A face whose cdf entry

@@ -30,7 +30,7 @@ DEV = "cuda:0"
 GRAD_TOL = 2e-4          # test_gpu_losses.GRAD_TOL
 VALUE_TOL = 1e-5         # test_gpu_losses.VALUE_TOL
 TILE_W, TILE_H = 64, 16  # ags.hip AG_TW x AG_TH: one workgroup per tile, a two-pixel halo of reciprocals around it
-FOLD = 256               # ags.hip AG_FOLD: partials (= workgroups) the fold kernel adds per trip
+FOLD = 256               # ags.hip AG_THREADS: partials (= workgroups) dns_fold_partials takes per trip in the fold kernel
 EDGES, CONFIDENCE = 8000, 20000          # a step of each mode with the weight on (7000 < step < 15000 <= step)
 LAMBDA, MASK_STEPS = 0.1, 15000
 

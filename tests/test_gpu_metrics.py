@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SPAN = 1024              # metrics.hip MT_SPAN: pixels per workgroup of the sweep
 HSPAN = 4096             # metrics.hip MT_HSPAN: elements per workgroup of rounds two and three
-FOLD = 256               # metrics.hip MT_FOLD: partials the last launch takes per trip
+FOLD = 256               # metrics.hip MT_THREADS: partials dns_fold_partials takes per trip in the last launch
 PAIRS = ("rgb", "depth", "normal")
 
 
