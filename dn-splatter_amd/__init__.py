@@ -37,6 +37,8 @@ from .geometry import (PDMetrics, calculate_accuracy, calculate_completeness, cl
                        mesh_metrics, sample_mesh_surface)
 from . import mesh_cull, torch_mesh_cull  # noqa: F401
 from .mesh_cull import cull_mesh, culled_mesh_metrics, cut_mesh, render_mesh_depth, vertex_visibility  # noqa: F401
+from . import tsdf, torch_tsdf  # noqa: F401
+from .tsdf import TSDFVolume, fuse_tsdf_mesh  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -50,5 +52,6 @@ __all__ = [
     "geometry", "torch_geometry", "PDMetrics", "calculate_accuracy", "calculate_completeness", "cloud_distances", "cloud_metrics",
     "install_pd_metrics", "mesh_metrics", "sample_mesh_surface",
     "mesh_cull", "torch_mesh_cull", "cull_mesh", "culled_mesh_metrics", "cut_mesh", "render_mesh_depth", "vertex_visibility",
+    "tsdf", "torch_tsdf", "TSDFVolume", "fuse_tsdf_mesh",
     "build_library", "load_library", "DnsplatError",
 ]

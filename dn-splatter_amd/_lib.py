@@ -201,6 +201,20 @@ class McArgs(ctypes.Structure):
     ]
 
 
+class McObservedArgs(ctypes.Structure):
+    _fields_ = [("mc", McArgs), ("weight", c_void_p), ("min_weight", c_float)]
+
+
+class TsdfArgs(ctypes.Structure):
+    _fields_ = [
+        ("tsdf", c_void_p), ("weight", c_void_p), ("color", c_void_p), ("nx", c_int32), ("ny", c_int32), ("nz", c_int32),
+        ("origin", ctypes.c_double * 3), ("voxel", ctypes.c_double), ("C", c_int32), ("width", c_int32), ("height", c_int32),
+        ("w2c", c_void_p), ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+        ("pixel_offset", ctypes.c_double), ("depth", c_void_p), ("rgb", c_void_p), ("ray_scale", c_void_p),
+        ("sdf_trunc", c_float), ("depth_trunc", c_float),
+    ]
+
+
 class CloudDistancesArgs(ctypes.Structure):
     _fields_ = [
         ("N", c_int32), ("index", c_void_p), ("M", c_int64), ("src", c_void_p), ("src_normals", c_void_p), ("tgt_normals", c_void_p),
@@ -276,6 +290,9 @@ EXPORTS = [
     # likewise: the mesh visibility culling (depth renders, vertex votes, the cut)
     "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_depth", "dnsplat_mesh_visibility", "dnsplat_mesh_cut_scratch_bytes",
     "dnsplat_mesh_cut_count", "dnsplat_mesh_cut_emit",
+    # likewise: TSDF fusion (frames into a volume, vertex colours) and marching cubes over the observed part of a lattice
+    "dnsplat_tsdf_integrate", "dnsplat_tsdf_vertex_colors", "dnsplat_mc_observed_scratch_bytes", "dnsplat_mc_count_observed",
+    "dnsplat_mc_emit_observed",
 ]
 
 _lib = None
@@ -392,12 +409,18 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_mesh_cut_scratch_bytes.argtypes = [c_int32, c_int32]
         L.dnsplat_mesh_cut_count.argtypes = [ctypes.POINTER(MeshCutArgs), c_void_p]
         L.dnsplat_mesh_cut_emit.argtypes = [ctypes.POINTER(MeshCutArgs), c_void_p]
+        L.dnsplat_tsdf_integrate.argtypes = [ctypes.POINTER(TsdfArgs), c_void_p]
+        L.dnsplat_tsdf_vertex_colors.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]
+        L.dnsplat_mc_observed_scratch_bytes.restype = c_size_t
+        L.dnsplat_mc_observed_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
+        L.dnsplat_mc_count_observed.argtypes = [ctypes.POINTER(McObservedArgs), c_void_p]
+        L.dnsplat_mc_emit_observed.argtypes = [ctypes.POINTER(McObservedArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
                             "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
                             "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
-                            "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes"):
+                            "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

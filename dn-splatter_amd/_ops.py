@@ -12,7 +12,7 @@ dn_model.py:543-560 does in torch; ``_RasterFn`` fuses isect_tiles + sort + rast
 get_outputs path).  ``_PackFn`` is the front end of the legacy rasterize_gaussians call.
 
 One builder per C struct: ``_scene_struct``, ``_camera_struct``, ``_ShLayout`` + ``_proj_grads``, ``_raster_args``, ``bin_tiles``'
-``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``, ``_mc_args``, ``_cloud_distances_args``, ``_mesh_sample_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
+``enqueue``, ``_backproject_args``, ``_eval_metrics_args``, ``_density_args``, ``_level_rays_args``, ``_level_points_args``, ``_mc_args``, ``_mc_observed_args``, ``_tsdf_args``, ``_cloud_distances_args``, ``_mesh_sample_args``; ``_ProjectFn.backward`` loops over the cameras in one of the four modes of ``_ProjBwd``.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, MeshCutArgs, MeshDepthArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshCutArgs, MeshDepthArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -424,6 +424,27 @@ def _mc_args(volume, level, scratch, counts, vertices=None, triangles=None, cap_
     a.counts = _ptr(counts)
     a.cap_v, a.cap_t = cap_v, cap_t
     a.vertices, a.triangles, a.status = _ptr(vertices), _ptr(triangles), _ptr(status)
+    return a
+
+
+def _mc_observed_args(weight, min_weight, *mc):
+    a = McObservedArgs()
+    a.mc = _mc_args(*mc)
+    a.weight, a.min_weight = _ptr(weight), min_weight
+    return a
+
+
+def _tsdf_args(tsdf, weight, color, origin, voxel, w2c, k, pixel_offset, depth, rgb, ray_scale, sdf_trunc, depth_trunc):
+    a = TsdfArgs()
+    a.tsdf, a.weight, a.color = _ptr(tsdf), _ptr(weight), _ptr(color)
+    a.nx, a.ny, a.nz = tsdf.shape
+    a.origin, a.voxel = (ctypes.c_double * 3)(*origin), voxel
+    a.C, a.height, a.width = depth.shape
+    a.w2c = _ptr(w2c)
+    a.fx, a.fy, a.cx, a.cy = k[0], k[4], k[2], k[5]
+    a.pixel_offset = pixel_offset
+    a.depth, a.rgb, a.ray_scale = _ptr(depth), _ptr(rgb), _ptr(ray_scale)
+    a.sdf_trunc, a.depth_trunc = sdf_trunc, depth_trunc
     return a
 
 

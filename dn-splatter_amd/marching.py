@@ -14,6 +14,10 @@ they are kept.  Nothing here is pinned to ``mcubes``: it is a third-party librar
     reference's exporter at;
   * ``marching_cubes_mesh(field, resolution, radius, ...)``: lines 740-800 — lattice, surface, world mapping, vertex colours.
 
+``weight`` / ``min_weight`` on ``mc_count`` and ``marching_cubes`` restrict the extraction to the observed part of the lattice
+(``weight > min_weight``; ``dnsplat_mc_count_observed`` / ``dnsplat_mc_emit_observed``, the rule of ``torch_marching``): the surface of
+a TSDF volume (``tsdf.TSDFVolume.extract_mesh``).  Without them the calls, the scratch and the bytes are what they always were.
+
 V and T depend on the data.  ``marching_cubes`` without ``capacity`` reads the two counts on the host once, between count and emit:
 ONE synchronisation per mesh, the only one.  With ``capacity=(cap_v, cap_t)`` nothing is read on the host; the caller checks
 ``status`` afterwards.  Simplification, cluster filtering and PLY output stay with the caller.  There is no CPU fallback."""
@@ -28,7 +32,7 @@ from torch import Tensor
 
 from . import _lib
 from ._lib import DnsplatError
-from ._ops import _f32c, _mc_args, _need_gpu, _stream
+from ._ops import _f32c, _mc_args, _mc_observed_args, _need_gpu, _stream
 from .density import GaussianDensityField, density_volume
 from .torch_marching import MAX_POINTS
 
@@ -36,11 +40,14 @@ STATUS_VERTICES, STATUS_TRIANGLES = 1, 2        # include/dnsplat.h DNSPLAT_MC_S
 
 
 class MarchingCount(NamedTuple):
-    """What ``mc_count`` leaves for ``mc_emit``: the lattice, the level, the scratch with masks and offsets, counts = int64 [2] (V, T)."""
+    """What ``mc_count`` leaves for ``mc_emit``: the lattice, the level, the scratch with masks and offsets, counts = int64 [2] (V, T);
+    ``weight`` / ``min_weight`` if the count was over the observed part only."""
     volume: Tensor
     level: float
     scratch: Optional[Tensor]
     counts: Tensor
+    weight: Optional[Tensor] = None
+    min_weight: float = 0.0
 
 
 class MarchingBuffers(NamedTuple):
@@ -60,18 +67,33 @@ def _lattice(volume: Tensor) -> Tensor:
     return volume
 
 
-def scratch_bytes(shape) -> int:
-    return int(_lib.lib().dnsplat_mc_scratch_bytes(*(int(s) for s in shape)))
-
-
-def mc_count(volume: Tensor, level: float, scratch: Optional[Tensor] = None) -> MarchingCount:
-    """``dnsplat_mc_count``: masks, per-word counts and their scan into ``scratch`` (allocated if not given), V and T into a device
-    int64 [2].  Four launches, nothing read on the host."""
-    volume = _lattice(volume)
+def scratch_bytes(shape, observed: bool = False) -> int:
     L = _lib.lib()
+    return int((L.dnsplat_mc_observed_scratch_bytes if observed else L.dnsplat_mc_scratch_bytes)(*(int(s) for s in shape)))
+
+
+def _run(name: str, count: "MarchingCount", a) -> None:
+    """``dnsplat_mc_<name>`` on McArgs ``a``, or ``dnsplat_mc_<name>_observed`` if the count carries a weight lattice."""
+    L = _lib.lib()
+    if count.weight is None:
+        _lib.run("dnsplat_mc_" + name, getattr(L, "dnsplat_mc_" + name), ctypes.byref(a), _stream())
+    else:
+        _lib.run("dnsplat_mc_" + name + "_observed", getattr(L, "dnsplat_mc_" + name + "_observed"), ctypes.byref(a), _stream())
+
+
+def mc_count(volume: Tensor, level: float, scratch: Optional[Tensor] = None, weight: Optional[Tensor] = None,
+             min_weight: float = 0.0) -> MarchingCount:
+    """``dnsplat_mc_count``: masks, per-word counts and their scan into ``scratch`` (allocated if not given), V and T into a device
+    int64 [2].  Four launches, nothing read on the host.  With ``weight`` (float32, the volume's shape):
+    ``dnsplat_mc_count_observed`` over the points with ``weight > min_weight``; ``scratch`` is then ``scratch_bytes(shape, True)``."""
+    volume = _lattice(volume)
+    if weight is not None:
+        weight = _f32c(weight.detach(), "weight")
+        if weight.shape != volume.shape or weight.device != volume.device:
+            raise ValueError(f"weight must be {tuple(volume.shape)} on {volume.device}, got {tuple(weight.shape)} on {weight.device}")
     counts = torch.empty(2, dtype=torch.int64, device=volume.device)
     if min(volume.shape) >= 2:
-        need = scratch_bytes(volume.shape)
+        need = scratch_bytes(volume.shape, weight is not None)
         if scratch is None:
             scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=volume.device)
         else:
@@ -80,12 +102,17 @@ def mc_count(volume: Tensor, level: float, scratch: Optional[Tensor] = None) -> 
                 raise ValueError(f"scratch must be a contiguous, 16-byte aligned buffer of at least {need} bytes")
     elif volume.numel() == 0:
         counts.zero_()
-        return MarchingCount(volume, float(level), None, counts)
+        return MarchingCount(volume, float(level), None, counts, weight, float(min_weight))
     else:
         scratch = None
-    a = _mc_args(volume, float(level), scratch, counts)
-    _lib.run("dnsplat_mc_count", L.dnsplat_mc_count, ctypes.byref(a), _stream())
-    return MarchingCount(volume, float(level), scratch, counts)
+    count = MarchingCount(volume, float(level), scratch, counts, weight, float(min_weight))
+    _run("count", count, _args(count))
+    return count
+
+
+def _args(count: MarchingCount, *emit):
+    mc = (count.volume, count.level, count.scratch, count.counts) + emit
+    return _mc_args(*mc) if count.weight is None else _mc_observed_args(count.weight, count.min_weight, *mc)
 
 
 def mc_emit(count: MarchingCount, vertices: Tensor, triangles: Tensor, cap_v: Optional[int] = None, cap_t: Optional[int] = None) -> Tensor:
@@ -103,21 +130,20 @@ def mc_emit(count: MarchingCount, vertices: Tensor, triangles: Tensor, cap_v: Op
     status = torch.empty(1, dtype=torch.int32, device=count.volume.device)
     if count.volume.numel() == 0:
         return status.zero_()
-    a = _mc_args(count.volume, count.level, count.scratch, count.counts, vertices if cap_v else None, triangles if cap_t else None,
-                 cap_v, cap_t, status)
-    L = _lib.lib()
-    _lib.run("dnsplat_mc_emit", L.dnsplat_mc_emit, ctypes.byref(a), _stream())
+    _run("emit", count, _args(count, vertices if cap_v else None, triangles if cap_t else None, cap_v, cap_t, status))
     return status
 
 
-def marching_cubes(volume: Tensor, level: float, capacity: Optional[Tuple[int, int]] = None):
-    """The iso-surface of ``volume`` (float32 [Rx,Ry,Rz] on the GPU, ``meshgrid(indexing="ij")`` order) at ``level``.
+def marching_cubes(volume: Tensor, level: float, capacity: Optional[Tuple[int, int]] = None, weight: Optional[Tensor] = None,
+                   min_weight: float = 0.0):
+    """The iso-surface of ``volume`` (float32 [Rx,Ry,Rz] on the GPU, ``meshgrid(indexing="ij")`` order) at ``level``; with ``weight``,
+    of the part of it where ``weight > min_weight`` (the module docstring).
 
     Without ``capacity``: (vertices float32 [V,3] in lattice coordinates, triangles int32 [T,3]); the two counts are read on the host
     once, between count and emit — one synchronisation per mesh.  With ``capacity=(cap_v, cap_t)``: a ``MarchingBuffers`` of
     full-capacity buffers, the device counts and the device status word, with no host read at all; rows past the counts are
     unwritten and a non-zero status means a capacity was too small (the rows below it are still the mesh's)."""
-    count = mc_count(volume, level)
+    count = mc_count(volume, level, weight=weight, min_weight=min_weight)
     dev = count.volume.device
     if capacity is not None:
         cap_v, cap_t = (int(c) for c in capacity)

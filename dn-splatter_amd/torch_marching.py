@@ -11,6 +11,11 @@ It is the yardstick the kernels are held to with exact equality, so the contract
   * triangles are int32 vertex ids; cells in ascending flat index of their lowest corner, within a cell in the table's order; the
     right-hand normal points towards decreasing value;
   * a corner equal to ``level`` gives ``t`` = 0 or 1 and zero-area triangles.  They are kept, as any table-driven extractor keeps them.
+
+With ``observed`` (a boolean lattice; for a TSDF volume ``weight > min_weight`` in float32) the extraction covers only what was seen,
+Open3D's rule for such a volume: an edge owns a vertex iff both its ends are observed and differ in the test, a cell has its table
+case iff all eight corners are observed (else none), numbering and order as above.  The value of an unobserved point never reaches
+a result.  Every triangle's vertices exist; at the rim of the observed region a vertex may be referenced by no triangle and stays.
 """
 from __future__ import annotations
 
@@ -56,8 +61,17 @@ def _volume(volume) -> np.ndarray:
     return volume
 
 
-def marching_cubes(volume, level):
-    """(vertices float32 [V,3] in lattice coordinates, triangles int32 [T,3]) as numpy arrays."""
+def _observed(observed, shape) -> np.ndarray:
+    if torch.is_tensor(observed):
+        observed = observed.detach().cpu().numpy()
+    observed = np.asarray(observed)
+    if observed.dtype != np.bool_ or observed.shape != shape:
+        raise ValueError(f"observed must be a boolean lattice of shape {shape}, got {observed.dtype} {observed.shape}")
+    return observed
+
+
+def marching_cubes(volume, level, observed=None):
+    """(vertices float32 [V,3] in lattice coordinates, triangles int32 [T,3]) as numpy arrays; ``observed``: see the module docstring."""
     v = _volume(volume)
     level = np.float32(level)
     Rx, Ry, Rz = v.shape
@@ -66,11 +80,18 @@ def marching_cubes(volume, level):
     if min(Rx, Ry, Rz) < 2:
         return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
     above = v > level
+    if observed is not None:
+        seen = _observed(observed, v.shape)
+        above = above & seen
     strides = (Ry * Rz, Rz, 1)
     cross = np.zeros((Rx, Ry, Rz, 3), dtype=bool)
     cross[:-1, :, :, 0] = above[:-1] != above[1:]
     cross[:, :-1, :, 1] = above[:, :-1] != above[:, 1:]
     cross[:, :, :-1, 2] = above[:, :, :-1] != above[:, :, 1:]
+    if observed is not None:
+        cross[:-1, :, :, 0] &= seen[:-1] & seen[1:]
+        cross[:, :-1, :, 1] &= seen[:, :-1] & seen[:, 1:]
+        cross[:, :, :-1, 2] &= seen[:, :, :-1] & seen[:, :, 1:]
     keys = np.flatnonzero(cross.reshape(-1))                # ascending (flat index of p, axis)
     p, a = keys // 3, keys % 3
     V = keys.size
@@ -93,6 +114,10 @@ def marching_cubes(volume, level):
     for c in range(8):
         di, dj, dk = c & 1, (c >> 1) & 1, (c >> 2) & 1
         case |= above[di:Rx - 1 + di, dj:Ry - 1 + dj, dk:Rz - 1 + dk].astype(np.int64) << c
+    if observed is not None:
+        for c in range(8):                                  # a cell with an unobserved corner has no case
+            di, dj, dk = c & 1, (c >> 1) & 1, (c >> 2) & 1
+            case[~seen[di:Rx - 1 + di, dj:Ry - 1 + dj, dk:Rz - 1 + dk]] = 0
     ii, jj, kk = np.nonzero(ntri[case] > 0)                 # C order: ascending flat index of the lowest corner
     cells = (ii * Ry + jj) * Rz + kk
     cc = case[ii, jj, kk]

@@ -4,6 +4,9 @@ argument struct (alive at that moment) is replayed against every variant library
 Box-to-box and run-to-run drift (2-3 % on this pool) cancels; the minimum and median per variant are printed.
 
     python tools/ab_kernels.py --entry dnsplat_raster_bwd --libs gpurun_ab/lib_base.so,gpurun_ab/lib_sym.so [--workload c2]
+
+``--workload mc256`` / ``mc512``: instead of the frame, ``marching_cubes`` at level 0.5 on the density lattice of the C2 scene
+(tools/marching_time.py's), for ``--entry dnsplat_mc_count`` or ``dnsplat_mc_emit``.
 """
 import argparse
 import ctypes
@@ -25,7 +28,7 @@ ap.add_argument("--rounds", type=int, default=12)
 ap.add_argument("--iters", type=int, default=4)
 args = ap.parse_args()
 WL = {"c2": (1_000_000, 1920, 1080), "c3": (3_000_000, 1600, 1200), "c5": (5_000_000, 1600, 1200)}
-N, W, H = WL[args.workload]
+N, W, H = WL.get(args.workload, WL["c2"])
 dev = "cuda:0"
 paths = [os.path.abspath(p) for p in args.libs.split(",")]
 libs = [(os.path.basename(p), ctypes.CDLL(p)) for p in paths]
@@ -60,6 +63,22 @@ def run(name, fn, *a):
 
 
 _lib.run = run
+if args.workload.startswith("mc"):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import marching_time  # noqa: E402
+
+    from dn_splatter_amd import marching  # noqa: E402
+
+    _, volume = marching_time.lattice(int(args.workload[2:]))
+    for it in range(2):
+        armed = it == 1                    # first mesh: warm-up with the default library only
+        marching.marching_cubes(volume, marching_time.LEVEL)
+    torch.cuda.synchronize()
+    for n, _ in libs:
+        t = results[n]
+        print(f"{args.entry} {args.workload} {n:28s} median {statistics.median(t):.4f} ms  min {min(t):.4f} ms  "
+              f"({100 * (statistics.median(t) / statistics.median(results[libs[0][0]]) - 1):+.2f} % vs first)")
+    sys.exit(0)
 gp = synthetic.make_gauss_params(N, sh_rest_std=0.1, seed=0, device=dev)
 cam = synthetic.orbit_camera(0, n_views=8, width=W, height=H, focal=1200.0).to(dev)
 r = dns.DNSplatterRenderer(gp, fused=True)
