@@ -35,29 +35,20 @@
 namespace {
 
 constexpr int RS_THREADS = 256;                  // 4 waves per workgroup
-#ifndef DNS_RS_ITEMS_I
-#define DNS_RS_ITEMS_I 16
-#endif
-constexpr int RS_ITEMS_I = DNS_RS_ITEMS_I;       // keys per lane in the I-sized tile passes: 4096 per workgroup (paired A/B at C2 / C3:
+constexpr int RS_ITEMS_I = 16;                   // keys per lane in the I-sized tile passes: 4096 per workgroup (paired A/B at C2 / C3:
                                                  // 8 -> +7 % / +2 %, 32 -> +29 % / +24 % of the emit + sort time)
-#ifndef DNS_RS_ITEMS_N
-#define DNS_RS_ITEMS_N 8
-#endif
-constexpr int RS_ITEMS_N = DNS_RS_ITEMS_N;       // ... in the N-sized depth passes: 1 M keys are only 245 chunks of 4096, less than
+constexpr int RS_ITEMS_N = 8;                    // ... in the N-sized depth passes: 1 M keys are only 245 chunks of 4096, less than
                                                  // one workgroup per CU and a 16-round ranking chain each; 2048-key chunks fill the chip (measured best of 2/4/8/16)
 // ... and twice that from 4 M entries on: with 2048-key chunks a 5 M-Gaussian depth sort is 2400 chunks per pass — the chip is full
 // either way, and 4096-key chunks halve the per-chunk tables the scans walk and double the scatter's run length (paired, round 4:
 // binning 0.659 -> 0.634 ms at 5 M, +-0 at 3 M; 8 stays the better choice at 1 M)
-constexpr int RS_ITEMS_N_LARGE = 2 * DNS_RS_ITEMS_N;
+constexpr int RS_ITEMS_N_LARGE = 2 * RS_ITEMS_N;
 constexpr int RS_LARGE_N = 1 << 22;
 inline int rs_items_n(int N) { return N >= RS_LARGE_N ? RS_ITEMS_N_LARGE : RS_ITEMS_N; }
 // the I-sized tile passes: the same 4096-key chunk as RS_THREADS x RS_ITEMS_I, cut into TI_THREADS x TI_ITEMS.  With 512 threads
 // the ranking chain of a wave (one LDS counter round trip per 64 keys) is 8 rounds long instead of 16 and a CU holds 24 instead
 // of 16 waves of this latency-bound kernel
-#ifndef DNS_TI_THREADS
-#define DNS_TI_THREADS 512
-#endif
-constexpr int TI_THREADS = DNS_TI_THREADS;
+constexpr int TI_THREADS = 512;
 constexpr int TI_ITEMS = RS_THREADS * RS_ITEMS_I / TI_THREADS;
 static_assert(TI_THREADS * TI_ITEMS == RS_THREADS * RS_ITEMS_I && TI_THREADS % DNS_WAVE == 0 && TI_THREADS >= 256, "tile-pass chunk");
 constexpr int RS_DIGITS = 256;
@@ -298,11 +289,8 @@ __global__ __launch_bounds__(TH) void radix_hist_kernel(const K *__restrict__ ke
 // The GEN histogram without generating a single pair (round 4; bin_ranges.h): every record that has pairs inside the workgroup's
 // chunk adds its box rows as cyclic digit RANGES to a difference array in LDS (two or three LDS atomics per box row instead of an
 // owner search, a 16-byte record gather and an LDS atomic per pair), a prefix sum turns the differences into the counts.  One thread
-// per record: the chunk's ~200 (C2) records are one round of coalesced 16-byte loads.  Same table as radix_hist_kernel<.., GEN>.
-// DNS_GEN_HIST_RANGES = 0 keeps the pair-generating histogram (A/B).
-#ifndef DNS_GEN_HIST_RANGES
-#define DNS_GEN_HIST_RANGES 1
-#endif
+// per record: the chunk's ~200 (C2) records are one round of coalesced 16-byte loads.  Same table as radix_hist_kernel<.., GEN>, which
+// no launch instantiates any more (docs/history.md §25).
 template <int ITEMS, int TH>
 __global__ __launch_bounds__(TH) void radix_hist_ranges_kernel(const uint32_t *__restrict__ n_ptr, uint32_t n_cap, int dbits,
                                                                uint32_t *__restrict__ table, int nb, int32_t *__restrict__ tile_first,
@@ -424,7 +412,7 @@ inline void scan_segments(int nb, int &segs, int &seg_len)
 #define DNS_TI_OCCUPANCY(th, K) __attribute__((amdgpu_waves_per_eu(((th) == 512 && sizeof(K) == 2) ? DNS_TI_WAVES_PER_EU : 1, 8)))
 // BOXG (round 6: the LAST pass of the depth sort): every value is a Gaussian id whose final depth rank `dst` is known here — its tile
 // box (dnsplat_proj_out.tile_boxes: one random 8-byte record) is gathered by this kernel and left behind in depth order together with
-// the tile count, instead of by scan_sums_kernel<true> afterwards: the 3.6 M random line fetches of a 5 M-Gaussian frame (92 us as a
+// the tile count, instead of by the gathering scan_sums_kernel afterwards: the 3.6 M random line fetches of a 5 M-Gaussian frame (92 us as a
 // kernel of their own) travel beside the scatter's own streams.
 template <typename K, bool LAST, int DBITS, int ITEMS, bool FIRST = false, bool GEN = false, int TH = RS_THREADS, bool BOXG = false>
 __global__ __launch_bounds__(TH) DNS_TI_OCCUPANCY(TH, K) void radix_scatter_kernel(
@@ -1048,6 +1036,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_bucket_sort_kernel(const uin
 // 8-byte gather per Gaussian yields both the count and the box; the box is left behind in depth order as well (boxes_sorted) and
 // emit_prep_kernel reads it coalesced instead of gathering it a second time through `order` (its random line per Gaussian was the
 // whole cost of that kernel: 73 us at 5 M Gaussians).  Two separate arrays gathered here cost 2 x a gather; one record does not.
+// Since round 6 the depth sort gathers the boxes itself and no launch instantiates BOXES = true (docs/history.md §25).
 template <bool BOXES>
 __global__ __launch_bounds__(SC_THREADS) void scan_sums_kernel(int N, const uint32_t *__restrict__ n_ptr,
                                                                const uint32_t *__restrict__ order,
@@ -1114,7 +1103,7 @@ struct EmitPrep {
     const int32_t *__restrict__ radii;
     const float4 *__restrict__ splats;   // tight tile boxes (dnsplat_bin_args.tight_tiles): the box the projection kernel counted
     const int2 *__restrict__ boxes;      // or NULL: (first tile id within the camera's grid, width | height << 16) straight from the projection
-    const int2 *__restrict__ boxes_sorted;   // the same records in depth order (scan_sums_kernel<true> left them): read by rank, no gather
+    const int2 *__restrict__ boxes_sorted;   // the same records in depth order (the depth sort left them): read by rank, no gather
 };
 
 // depth rank j = entry gid owns the pairs [start, end) of the emission order, end > start
@@ -1126,6 +1115,7 @@ __device__ __forceinline__ void emit_record(const EmitPrep &ep, int N, uint32_t 
     // cameras' (tile id = camera * tw * th + row * tw + column)
     const uint32_t cam_tiles = (ep.n_per_cam < N) ? (gid / (uint32_t)ep.n_per_cam) * (uint32_t)(ep.tw * ep.th) : 0u;
     if (ep.boxes) {
+        // boxes always comes with boxes_sorted (dnsplat_bin_prepare): the second arm is never taken
         const int2 b = ep.boxes_sorted ? ep.boxes_sorted[j] : ep.boxes[gid];
         r.bw = (uint32_t)b.y & 0xffffu;
         r.base_tile = (uint32_t)b.x + cam_tiles;
@@ -1341,53 +1331,102 @@ BinWs carve(void *ws, int N, int64_t cap)
 
 int tile_bits(int n_tiles);
 
-// one LSD pass over `dbits` bits at `shift`; tile_first != nullptr marks the last pass of the tile sort;
-// gen != nullptr: the first pass of the tile sort, whose input is generated (no ka / va)
-template <typename K, int ITEMS, int TH = RS_THREADS>
-void radix_pass(hipStream_t stream, const K *ka, const uint32_t *va, K *kb, uint32_t *vb, const uint32_t *n_ptr,
-                uint32_t n_cap, int shift, int dbits, uint32_t *table, uint32_t *totals, int nb, int32_t *tile_first = nullptr,
-                const int32_t *radii = nullptr, const float *depths = nullptr, int32_t *init_offsets = nullptr, int n_tiles = 0,
-                int32_t *tile_end = nullptr, const GenArgs *gen = nullptr, uint32_t *status = nullptr, uint32_t *count_out = nullptr,
-                const int2 *box_in = nullptr, int2 *box_out = nullptr, uint32_t *tiles_out = nullptr)
+// ------------------------------------------------------------------------------------------------
+// The three kinds of LSD radix pass.  Each is histogram, digit scan, stable scatter — the n = min(*n_ptr, n_cap) keys of (ka, va) go to
+// (kb, vb) by the `dbits` bits at `shift` — and each instantiates exactly the kernels it launches.
+struct DigitTable {
+    uint32_t *table;     // [digits x nb] digit counts per chunk
+    uint32_t *totals;    // [digits x SC_MAX_SEGS] segment sums of their scan
+    int nb;              // chunks
+};
+
+// the digit scan between a pass's histogram and its scatter, which has to know the segments
+struct ScanSegs { int segs, seg_len; };
+inline ScanSegs scan_digits(hipStream_t stream, const DigitTable &t, int dbits)
 {
-    const uint32_t mask = (1u << dbits) - 1u;
-    int segs, seg_len;
-    scan_segments(nb, segs, seg_len);
-    if (radii) {   // first pass of the depth sort: 8-bit digit, keys synthesised from (radii, depths)
-        hipLaunchKernelGGL((radix_hist_kernel<K, ITEMS, true, false, TH>), dim3(nb), dim3(TH), 0, stream, ka, n_ptr, n_cap, shift, mask, table, nb, radii, depths);
-        hipLaunchKernelGGL(radix_scan_kernel, dim3((1 << dbits) * segs), dim3(SC_THREADS), 0, stream, table, nb, totals, segs, seg_len);
-        hipLaunchKernelGGL((radix_scatter_kernel<K, false, 8, ITEMS, true, false, TH>), dim3(nb), dim3(TH), 0, stream, ka, va, kb, vb,
-                           n_ptr, n_cap, shift, table, totals, nb, tile_first, radii, depths, (int32_t *)nullptr, GenArgs{}, count_out,
-                           (const int2 *)nullptr, (int2 *)nullptr, (uint32_t *)nullptr, segs, seg_len);
-        return;
-    }
-    const GenArgs g = gen ? *gen : GenArgs{};
-    if (gen && DNS_GEN_HIST_RANGES && shift == 0 && TH > RS_DIGITS)
-        hipLaunchKernelGGL((radix_hist_ranges_kernel<ITEMS, (TH > RS_DIGITS ? TH : 2 * RS_DIGITS)>), dim3(nb), dim3(TH), 0, stream, n_ptr, n_cap, dbits,
-                           table, nb, init_offsets, n_tiles, init_offsets ? tile_end : nullptr, g, status);
-    else if (gen)
-        hipLaunchKernelGGL((radix_hist_kernel<K, ITEMS, false, true, TH>), dim3(nb), dim3(TH), 0, stream, ka, n_ptr, n_cap, shift, mask,
-                           table, nb, (const int32_t *)nullptr, (const float *)nullptr, init_offsets, n_tiles, init_offsets ? tile_end : nullptr, g, status);
+    ScanSegs s;
+    scan_segments(t.nb, s.segs, s.seg_len);
+    hipLaunchKernelGGL(radix_scan_kernel, dim3((1 << dbits) * s.segs), dim3(SC_THREADS), 0, stream, t.table, t.nb, t.totals, s.segs, s.seg_len);
+    return s;
+}
+
+// First pass of the four-pass depth sort, by the low 8 bits: reads (radii, depths) of the n entries (a count the host knows) instead of a
+// key / value pair, drops the culled Gaussians and leaves the number it kept in n_ranked, which bounds every later pass and the scans.
+template <int ITEMS>
+void depth_first_pass(hipStream_t stream, const int32_t *radii, const float *depths, uint32_t n, uint32_t *kb, uint32_t *vb,
+                      const DigitTable &t, uint32_t *n_ranked)
+{
+    hipLaunchKernelGGL((radix_hist_kernel<uint32_t, ITEMS, true, false, RS_THREADS>), dim3(t.nb), dim3(RS_THREADS), 0, stream, nullptr, nullptr, n,
+                       0, 0xffu, t.table, t.nb, radii, depths);
+    const ScanSegs s = scan_digits(stream, t, 8);
+    hipLaunchKernelGGL((radix_scatter_kernel<uint32_t, false, 8, ITEMS, true, false, RS_THREADS>), dim3(t.nb), dim3(RS_THREADS), 0, stream, nullptr,
+                       nullptr, kb, vb, nullptr, n, 0, t.table, t.totals, t.nb, nullptr, radii, depths, nullptr, GenArgs{}, n_ranked, nullptr,
+                       nullptr, nullptr, s.segs, s.seg_len);
+}
+
+// the tile boxes a depth pass gathers by the values it scatters (radix_scatter_kernel<.., BOXG>): left in depth order, with the tile counts
+struct BoxGather {
+    const int2 *boxes;
+    int2 *boxes_sorted;
+    uint32_t *tiles_sorted;
+};
+
+// A plain 8-bit pass over 32-bit keys: passes 1-3 of the four-pass depth sort and every pass of dnsplat_det_reduce.  gather: the box
+// gather folded into the scatter (the last depth pass), or NULL.
+template <int ITEMS>
+void depth_pass(hipStream_t stream, const uint32_t *ka, const uint32_t *va, uint32_t *kb, uint32_t *vb, const uint32_t *n_ptr, uint32_t n_cap,
+                int shift, const DigitTable &t, const BoxGather *gather)
+{
+    hipLaunchKernelGGL((radix_hist_kernel<uint32_t, ITEMS, false, false, RS_THREADS>), dim3(t.nb), dim3(RS_THREADS), 0, stream, ka, n_ptr, n_cap,
+                       shift, 0xffu, t.table, t.nb);
+    const ScanSegs s = scan_digits(stream, t, 8);
+    if (gather)
+        hipLaunchKernelGGL((radix_scatter_kernel<uint32_t, false, 8, ITEMS, false, false, RS_THREADS, true>), dim3(t.nb), dim3(RS_THREADS), 0, stream,
+                           ka, va, kb, vb, n_ptr, n_cap, shift, t.table, t.totals, t.nb, nullptr, nullptr, nullptr, nullptr, GenArgs{}, nullptr,
+                           gather->boxes, gather->boxes_sorted, gather->tiles_sorted, s.segs, s.seg_len);
     else
-        hipLaunchKernelGGL((radix_hist_kernel<K, ITEMS, false, false, TH>), dim3(nb), dim3(TH), 0, stream, ka, n_ptr, n_cap, shift, mask, table, nb,
-                           (const int32_t *)nullptr, (const float *)nullptr, init_offsets, n_tiles, init_offsets ? tile_end : nullptr, g, status);
-    hipLaunchKernelGGL(radix_scan_kernel, dim3((1 << dbits) * segs), dim3(SC_THREADS), 0, stream, table, nb, totals, segs, seg_len);
-    if constexpr (sizeof(K) == 4) {
-        if (box_in && !gen && !tile_first && dbits == 8) {      // last depth pass with the box gather folded in
-            hipLaunchKernelGGL((radix_scatter_kernel<K, false, 8, ITEMS, false, false, TH, true>), dim3(nb), dim3(TH), 0, stream, ka, va, kb, vb,
-                               n_ptr, n_cap, shift, table, totals, nb, tile_first, (const int32_t *)nullptr, (const float *)nullptr,
-                               (int32_t *)nullptr, GenArgs{}, (uint32_t *)nullptr, box_in, box_out, tiles_out, segs, seg_len);
-            return;
-        }
-    }
-#define DNS_SCATTER3(B, L, G)                                                                                               \
-    hipLaunchKernelGGL((radix_scatter_kernel<K, L, B, ITEMS, false, G, TH>), dim3(nb), dim3(TH), 0, stream, ka, va, kb, vb,    \
-                       n_ptr, n_cap, shift, table, totals, nb, tile_first, (const int32_t *)nullptr, (const float *)nullptr, \
-                       tile_end, g, (uint32_t *)nullptr, (const int2 *)nullptr, (int2 *)nullptr, (uint32_t *)nullptr, segs, seg_len)
+        hipLaunchKernelGGL((radix_scatter_kernel<uint32_t, false, 8, ITEMS, false, false, RS_THREADS, false>), dim3(t.nb), dim3(RS_THREADS), 0, stream,
+                           ka, va, kb, vb, n_ptr, n_cap, shift, t.table, t.totals, t.nb, nullptr, nullptr, nullptr, nullptr, GenArgs{}, nullptr,
+                           nullptr, nullptr, nullptr, s.segs, s.seg_len);
+}
+
+// what the passes of one tile sort share
+struct TileSort {
+    const uint32_t *n_ptr;       // the pairs: min(*n_ptr, n_cap)
+    uint32_t n_cap;
+    DigitTable t;
+    GenArgs gen;                 // the first pass generates its pairs from these instead of reading (ka, va)
+    int32_t *tile_offsets;       // [n_tiles + 1] preset by the first pass, lowered to the tiles' first entries by the last
+    int32_t *tile_ends;          // [n_tiles] or NULL, likewise
+    int n_tiles;
+    uint32_t *status;            // cleared by the first pass
+};
+
+// One pass of the tile sort over `dbits` (1..8) bits of the K-typed tile ids.  The first counts its digits from the records' box rows
+// (radix_hist_ranges_kernel) and generates the pairs in its scatter; the last stores no keys and yields the tile offsets.  A sort of one
+// pass is both.
+template <typename K>
+void tile_pass(hipStream_t stream, const TileSort &ts, const K *ka, const uint32_t *va, K *kb, uint32_t *vb, int shift, int dbits, bool first,
+               bool last)
+{
+    const DigitTable &t = ts.t;
+    if (first)
+        hipLaunchKernelGGL((radix_hist_ranges_kernel<TI_ITEMS, TI_THREADS>), dim3(t.nb), dim3(TI_THREADS), 0, stream, ts.n_ptr, ts.n_cap, dbits,
+                           t.table, t.nb, ts.tile_offsets, ts.n_tiles, ts.tile_ends, ts.gen, ts.status);
+    else
+        hipLaunchKernelGGL((radix_hist_kernel<K, TI_ITEMS, false, false, TI_THREADS>), dim3(t.nb), dim3(TI_THREADS), 0, stream, ka, ts.n_ptr,
+                           ts.n_cap, shift, (1u << dbits) - 1u, t.table, t.nb, nullptr, nullptr, nullptr, ts.n_tiles);
+    const ScanSegs s = scan_digits(stream, t, dbits);
+    const GenArgs g = first ? ts.gen : GenArgs{};
+    int32_t *tile_first = last ? ts.tile_offsets : nullptr;
+#define DNS_SCATTER3(B, L, G)                                                                                                             \
+    hipLaunchKernelGGL((radix_scatter_kernel<K, L, B, TI_ITEMS, false, G, TI_THREADS>), dim3(t.nb), dim3(TI_THREADS), 0, stream, ka, va, kb, vb, \
+                       ts.n_ptr, ts.n_cap, shift, t.table, t.totals, t.nb, tile_first, nullptr, nullptr, ts.tile_ends, g, nullptr, nullptr,  \
+                       nullptr, nullptr, s.segs, s.seg_len)
 #define DNS_SCATTER(B)                                                                                                      \
     do {                                                                                                                    \
-        if (tile_first) { if (gen) DNS_SCATTER3(B, true, true); else DNS_SCATTER3(B, true, false); }                        \
-        else { if (gen) DNS_SCATTER3(B, false, true); else DNS_SCATTER3(B, false, false); }                                 \
+        if (last) { if (first) DNS_SCATTER3(B, true, true); else DNS_SCATTER3(B, true, false); }                            \
+        else { if (first) DNS_SCATTER3(B, false, true); else DNS_SCATTER3(B, false, false); }                               \
     } while (0)
     switch (dbits) {
         case 1: DNS_SCATTER(1); break;
@@ -1413,10 +1452,14 @@ void emit_and_sort(hipStream_t stream, const dnsplat_bin_args *a, const BinWs &w
     const int n_cam = a->n_cameras > 1 ? a->n_cameras : 1;
     const int bits = tile_bits(n_tiles);
     const int passes = (bits + 7) / 8;
-    GenArgs g;
-    g.jrec = w.jrec; g.cum = w.cum; g.chunk_first = w.chunk_first;
-    g.N = a->N; g.tw = tw; g.n_ranked = w.n_ranked;
-    g.exact = (tw <= 256 && (int64_t)n_cam * tw * th <= 65536) ? 1 : 0;
+    TileSort ts;
+    ts.n_ptr = w.total; ts.n_cap = cap;
+    ts.t = DigitTable{w.tab_i, w.totals, w.nb_i};
+    ts.gen.jrec = w.jrec; ts.gen.cum = w.cum; ts.gen.chunk_first = w.chunk_first;
+    ts.gen.N = a->N; ts.gen.tw = tw; ts.gen.n_ranked = w.n_ranked;
+    ts.gen.exact = (tw <= 256 && (int64_t)n_cam * tw * th <= 65536) ? 1 : 0;
+    ts.tile_offsets = a->tile_offsets; ts.tile_ends = a->tile_ends; ts.n_tiles = n_tiles;
+    ts.status = w.status;
     const K *ka = nullptr;
     const uint32_t *va = nullptr;
     int shift = 0;
@@ -1425,15 +1468,30 @@ void emit_and_sort(hipStream_t stream, const dnsplat_bin_args *a, const BinWs &w
         const bool last = pass == passes - 1;
         K *kout = (pass & 1) ? kc : kb;
         uint32_t *vout = last ? (uint32_t *)a->flatten_ids : ((pass & 1) ? vc : vb);
-        radix_pass<K, TI_ITEMS, TI_THREADS>(stream, ka, va, kout, vout, w.total, cap, shift, dbits, w.tab_i, w.totals, w.nb_i,
-                                  last ? a->tile_offsets : nullptr, nullptr, nullptr, pass == 0 ? a->tile_offsets : nullptr, n_tiles,
-                                  a->tile_ends, pass == 0 ? &g : nullptr, pass == 0 ? w.status : nullptr);
+        tile_pass<K>(stream, ts, ka, va, kout, vout, shift, dbits, pass == 0, last);
         shift += dbits;
         ka = kout; va = vout;
     }
     // the offsets of the empty tiles (gsplat's isect_offsets): a consumer that takes tile_ends as well does not need them
     if (!(a->tile_ends && a->skip_offsets_fill))
         hipLaunchKernelGGL(tile_offsets_fill_kernel, dim3(1), dim3(TO_THREADS), 0, stream, n_tiles, a->tile_offsets);
+}
+
+// The four-pass depth sort of dnsplat_bin_prepare: leaves the depth order in w.val_a.  boxes != NULL: the last pass leaves the tile boxes
+// and the tile counts in depth order beside it.
+template <int ITEMS>
+void depth_sort_radix4(hipStream_t stream, const dnsplat_bin_args *a, const BinWs &w, const int2 *boxes)
+{
+    const DigitTable t{w.tab_n, w.totals, w.nb_n};
+    const BoxGather gather{boxes, w.boxes_sorted, w.tiles_sorted};
+    const uint32_t n = (uint32_t)a->N;
+    uint32_t *ka = w.key_a, *kb = w.key_b, *va = w.val_a, *vb = w.val_b;
+    for (int pass = 0; pass < 4; ++pass) {
+        if (pass == 0) depth_first_pass<ITEMS>(stream, a->radii, a->depths, n, kb, vb, t, w.n_ranked);
+        else depth_pass<ITEMS>(stream, ka, va, kb, vb, w.n_ranked, n, 8 * pass, t, boxes && pass == 3 ? &gather : nullptr);
+        uint32_t *x = ka; ka = kb; kb = x;
+        x = va; va = vb; vb = x;
+    }
 }
 
 int tile_bits(int n_tiles)
@@ -1528,8 +1586,9 @@ extern "C" int dnsplat_det_reduce(const dnsplat_det_args *a, dnsplat_stream_t st
     const int passes = (bits + 7) / 8;
     const uint32_t *ka = reinterpret_cast<const uint32_t *>(a->flatten_ids);
     uint32_t *va = w.val_a, *kb = w.key_a, *vb = w.val_b;
+    const DigitTable t{w.table, w.totals, w.nb};
     for (int pass = 0; pass < passes; ++pass) {
-        radix_pass<uint32_t, RS_ITEMS_N>(stream, ka, va, kb, vb, w.count, cap, 8 * pass, 8, w.table, w.totals, w.nb);
+        depth_pass<RS_ITEMS_N>(stream, ka, va, kb, vb, w.count, cap, 8 * pass, t, nullptr);
         ka = kb; va = vb;
         kb = (kb == w.key_a) ? w.key_b : w.key_a;
         vb = (vb == w.val_b) ? w.val_a : w.val_b;
@@ -1597,16 +1656,10 @@ extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t s
         if (hipMemsetAsync(w.total, 0, sizeof(uint32_t), stream) != hipSuccess) return DNSPLAT_ERR_LAUNCH;
     } else {
         const uint32_t n_u32 = (uint32_t)N;
-        uint32_t *ka = w.key_a, *kb = w.key_b, *va = w.val_a, *vb = w.val_b;
+        // the projection's tile boxes, or NULL: the depth sort gathers them on the way (its last pass or its bucket sorts) and leaves them
+        // and the tile counts in depth order
         const int2 *boxes = reinterpret_cast<const int2 *>(a->tile_boxes);
-        // DNSPLAT_BIN_BOX_GATHER=0: the round-3 route (counts gathered here, boxes gathered again by emit_prep_kernel), for A/B runs
-        static const bool box_gather = [] { const char *e = getenv("DNSPLAT_BIN_BOX_GATHER"); return !(e && e[0] == '0'); }();
-        const bool sorted_boxes = boxes && box_gather;
-        // DNSPLAT_BIN_BOX_FOLD=0: the box gather as scan_sums_kernel<true> behind the depth sort (round 4 / 5) instead of inside its last pass
-        static const bool box_fold = [] { const char *e = getenv("DNSPLAT_BIN_BOX_FOLD"); return !(e && e[0] == '0'); }();
-        const bool fold = sorted_boxes && box_fold;
-        const bool radix4 = !depth_sort_by_partition(N);
-        if (!radix4) {
+        if (depth_sort_by_partition(N)) {
             uint2 *pairs_a = reinterpret_cast<uint2 *>(w.jrec), *pairs_b = pairs_a + N;
             const int n_part = dp_bounds_wgs(N), sub = dp_sub(N);
             int segs, seg_len;
@@ -1630,33 +1683,12 @@ extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t s
             }
 #undef DNS_DEPTH_PARTITION
             hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(1 << bbits), dim3(DP_THREADS), 0, stream, w.dp_ks, w.dp_start, pairs_a, pairs_b,
-                               w.val_a, fold ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
-        } else {
-            for (int pass = 0; pass < 4; ++pass) {
-                const int shift = 8 * pass;
-                const bool fold_here = fold && pass == 3;
-                // pass 0 knows its element count on the host (n_ptr = NULL), reads (radii, depths) instead of a key / value pair and drops
-                // the culled Gaussians; it leaves the number it kept in w.n_ranked, which bounds every later pass and the scans
-                if (rs_items_n(N) == RS_ITEMS_N_LARGE)
-                    radix_pass<uint32_t, RS_ITEMS_N_LARGE>(stream, ka, va, kb, vb, pass == 0 ? nullptr : w.n_ranked, n_u32, shift, 8, w.tab_n, w.totals,
-                                                           w.nb_n, nullptr, pass == 0 ? a->radii : nullptr, pass == 0 ? a->depths : nullptr, nullptr, 0,
-                                                           nullptr, nullptr, nullptr, pass == 0 ? w.n_ranked : nullptr,
-                                                           fold_here ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
-                else
-                    radix_pass<uint32_t, RS_ITEMS_N>(stream, ka, va, kb, vb, pass == 0 ? nullptr : w.n_ranked, n_u32, shift, 8, w.tab_n, w.totals,
-                                                     w.nb_n, nullptr, pass == 0 ? a->radii : nullptr, pass == 0 ? a->depths : nullptr, nullptr, 0,
-                                                     nullptr, nullptr, nullptr, pass == 0 ? w.n_ranked : nullptr,
-                                                     fold_here ? boxes : nullptr, w.boxes_sorted, w.tiles_sorted);
-                uint32_t *t = ka; ka = kb; kb = t;
-                t = va; va = vb; vb = t;
-            }
-        }
-        // either way the depth order is in val_a now
-        if (fold)
+                               w.val_a, boxes, w.boxes_sorted, w.tiles_sorted);
+        } else if (rs_items_n(N) == RS_ITEMS_N_LARGE) depth_sort_radix4<RS_ITEMS_N_LARGE>(stream, a, w, boxes);
+        else depth_sort_radix4<RS_ITEMS_N>(stream, a, w, boxes);
+        // either way the depth order is in val_a now, and with boxes the tile counts in tiles_sorted
+        if (boxes)
             hipLaunchKernelGGL(scan_sums_sorted_kernel, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.tiles_sorted, w.sums);
-        else if (sorted_boxes)
-            hipLaunchKernelGGL(scan_sums_kernel<true>, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.val_a, a->tiles_per_gauss,
-                               w.sums, w.tiles_sorted, boxes, w.boxes_sorted);
         else
             hipLaunchKernelGGL(scan_sums_kernel<false>, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.val_a, a->tiles_per_gauss,
                                w.sums, w.tiles_sorted);
@@ -1668,7 +1700,7 @@ extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t s
         ep.means2d = a->means2d; ep.radii = a->radii;
         ep.splats = a->tight_tiles ? reinterpret_cast<const float4 *>(a->splats) : nullptr;
         ep.boxes = boxes;
-        ep.boxes_sorted = sorted_boxes ? w.boxes_sorted : nullptr;
+        ep.boxes_sorted = boxes ? w.boxes_sorted : nullptr;
         hipLaunchKernelGGL(scan_final_kernel, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.val_a,
                            (const int32_t *)w.tiles_sorted, w.sums, w.cum, w.total, a->n_isects, a->n_isects_max);
         hipLaunchKernelGGL(emit_prep_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, w.n_ranked, w.val_a, w.cum, ep);

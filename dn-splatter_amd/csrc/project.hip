@@ -14,7 +14,7 @@
 // oracle/oracle_impl.inc spells out, without FMA contraction.  The kernel is bandwidth-trivial
 // (one thread per Gaussian, ~0.3 KB each way), so nothing is lost.
 //
-// Mapping: one lane per Gaussian, one wave per workgroup (DNS_PROJ_THREADS = 64: paired A/B against 128 / 256 threads at 1 M
+// Mapping: one lane per Gaussian, one wave per workgroup (SH_STAGE_THREADS = 64: paired A/B against 128 / 256 threads at 1 M
 // Gaussians: project_fwd -2 %, project_bwd -4 % — more workgroups per CU overlap their load / compute / store phases).  Camera
 // constants are read through wave-uniform pointers, i.e. they live in SGPRs.
 
@@ -276,10 +276,8 @@ __device__ __forceinline__ void gaussian_normal(const float *Rq, const float *sc
 // each lane walk its own LDS row (odd row stride => conflict-free ds_read_b32).  Two layouts:
 //   SPLIT  features_dc [N,3] + features_rest [N,15,3]   rows of 45 floats, span = features_rest
 //   CAT    colours [N,16,3] (gsplat layout)               rows of 48 floats incl. band 0, LDS stride 49
-#ifndef DNS_PROJ_THREADS
-#define DNS_PROJ_THREADS 64
-#endif
-constexpr int SH_STAGE_THREADS = DNS_PROJ_THREADS;      // threads (= Gaussians) per workgroup of the staged kernels
+constexpr int SH_STAGE_THREADS = DNS_WAVE;      // threads (= Gaussians) per workgroup of the staged kernels: one wave
+static_assert(SH_STAGE_THREADS == 64, "the row masks of the staged kernels are one 64-bit ballot");
 enum ShLayout { SH_DIRECT = 0, SH_SPLIT = 1, SH_CAT = 2 };
 template <int L> struct ShRowTraits { static constexpr int ROW = 45, LDS_ROW = 45; };
 template <> struct ShRowTraits<SH_CAT> { static constexpr int ROW = 48, LDS_ROW = 49; };
@@ -290,42 +288,28 @@ __device__ __forceinline__ int sh_lds_index(int e)
     return L == SH_CAT ? e + e / ShRowTraits<L>::ROW : e;
 }
 
-// DNS_PROJ_NT: the coefficient rows are read once and their gradients written once per frame, as one coalesced stream per
-// workgroup: 1 = non-temporal loads (they skip the CU's vector L1), 2 = non-temporal stores, 3 = both.  Inside the C2 frame
-// (library variants interleaved in whole bench runs): project_fwd -10 % with 3, -6 % with 1; project_bwd +-0 with 3, -3 % with 1.
-#ifndef DNS_PROJ_NT
-#define DNS_PROJ_NT 3
-#endif
-#ifndef DNS_PROJ_STAGED_REC
-#define DNS_PROJ_STAGED_REC 1
-#endif
+// The coefficient rows are read once and their gradients written once per frame, as one coalesced stream per workgroup: non-temporal
+// loads (they skip the CU's vector L1) and non-temporal stores.  Inside the C2 frame (library variants interleaved in whole bench
+// runs): project_fwd -10 % with both, -6 % with the loads alone; project_bwd +-0 with both, -3 % with the loads alone.
 typedef float dns_v4f __attribute__((ext_vector_type(4)));
 
-// DNS_PROJ_STAGE_UNROLL: all 16-byte loads of a workgroup's coefficient span are ISSUED before the first one is waited for.
-// Round 4 find, from the ISA: the rolled loop below compiled to  global_load_dwordx4 -> s_waitcnt vmcnt(0) -> ds_write_b128  per
+// All 16-byte loads of a workgroup's coefficient span are ISSUED before the first one is waited for.
+// Round 4 find, from the ISA: a rolled loop compiled to  global_load_dwordx4 -> s_waitcnt vmcnt(0) -> ds_write_b128  per
 // iteration — ONE kilobyte in flight per wave, twelve HBM round trips in a row per workgroup, 12 KB in flight per CU with the 12
 // waves the kernels' registers allow: about 3 MB on the whole chip where HBM needs bandwidth x latency = 6-8 MB.  That, not the
 // occupancy, is what held the per-Gaussian kernels at 3.7-4.3 TB/s.  Unrolled, a wave has its whole 11.5 KB span in flight.
-#ifndef DNS_PROJ_STAGE_UNROLL
-#define DNS_PROJ_STAGE_UNROLL 1
-#endif
 template <int L>
 __device__ __forceinline__ void sh_stage_in(const float *__restrict__ gbase, int nfloats, float *lds)
 {
     const dns_v4f *g4 = reinterpret_cast<const dns_v4f *>(gbase);
     const int n4 = nfloats >> 2;
-#if DNS_PROJ_STAGE_UNROLL
     constexpr int MAXIT = (SH_STAGE_THREADS * ShRowTraits<L>::ROW / 4 + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS;
     dns_v4f v[MAXIT];
 #pragma unroll
     for (int k = 0; k < MAXIT; ++k) {
         const int i = (int)threadIdx.x + k * SH_STAGE_THREADS;
         if (i < n4) {
-#if DNS_PROJ_NT & 1
             v[k] = __builtin_nontemporal_load(g4 + i);
-#else
-            v[k] = g4[i];
-#endif
         }
     }
 #pragma unroll
@@ -336,17 +320,6 @@ __device__ __forceinline__ void sh_stage_in(const float *__restrict__ gbase, int
             lds[o] = v[k].x; lds[o + 1] = v[k].y; lds[o + 2] = v[k].z; lds[o + 3] = v[k].w;
         }
     }
-#else
-    for (int i = threadIdx.x; i < n4; i += SH_STAGE_THREADS) {
-#if DNS_PROJ_NT & 1
-        const dns_v4f v = __builtin_nontemporal_load(g4 + i);
-#else
-        const dns_v4f v = g4[i];
-#endif
-        const int o = sh_lds_index<L>(4 * i);   // ROW % 4 == 0 in the padded layout: the 4 floats share a row
-        lds[o] = v.x; lds[o + 1] = v.y; lds[o + 2] = v.z; lds[o + 3] = v.w;
-    }
-#endif
     for (int e = (n4 << 2) + threadIdx.x; e < nfloats; e += SH_STAGE_THREADS) lds[sh_lds_index<L>(e)] = gbase[e];
 }
 
@@ -358,11 +331,7 @@ __device__ __forceinline__ void sh_stage_out(float *__restrict__ gbase, int nflo
     for (int i = threadIdx.x; i < n4; i += SH_STAGE_THREADS) {
         const int o = sh_lds_index<L>(4 * i);
         const dns_v4f v = {lds[o], lds[o + 1], lds[o + 2], lds[o + 3]};
-#if DNS_PROJ_NT & 2
         __builtin_nontemporal_store(v, g4 + i);
-#else
-        g4[i] = v;
-#endif
     }
     for (int e = (n4 << 2) + threadIdx.x; e < nfloats; e += SH_STAGE_THREADS) gbase[e] = lds[sh_lds_index<L>(e)];
 }
@@ -370,10 +339,7 @@ __device__ __forceinline__ void sh_stage_out(float *__restrict__ gbase, int nflo
 // Row-selective staging (round 6): `rows` = one bit per Gaussian of the workgroup (a wave: SH_STAGE_THREADS ==
 // 64).  A 16-byte piece is moved only if a selected row owns one of its floats — the coefficient rows of culled Gaussians (28 % on
 // the benchmark scenes) are neither read nor, once known to be zero, written again.  Rows are 180 bytes at a 180-byte stride, so a
-// skipped row saves the lines it does not share with a selected neighbour.  DNS_PROJ_VISIBLE_ROWS=0 restores whole-span staging.
-#ifndef DNS_PROJ_VISIBLE_ROWS
-#define DNS_PROJ_VISIBLE_ROWS 1
-#endif
+// skipped row saves the lines it does not share with a selected neighbour.
 template <int L>
 __device__ __forceinline__ bool sh_piece_selected(int piece, uint64_t rows)
 {
@@ -392,11 +358,7 @@ __device__ __forceinline__ void sh_stage_in_rows(const float *__restrict__ gbase
     for (int k = 0; k < MAXIT; ++k) {
         const int i = (int)threadIdx.x + k * SH_STAGE_THREADS;
         if (i < n4 && sh_piece_selected<L>(i, rows)) {
-#if DNS_PROJ_NT & 1
             v[k] = __builtin_nontemporal_load(g4 + i);
-#else
-            v[k] = g4[i];
-#endif
         }
     }
 #pragma unroll
@@ -419,11 +381,7 @@ __device__ __forceinline__ void sh_stage_out_rows(float *__restrict__ gbase, int
         if (!sh_piece_selected<L>(i, rows)) continue;
         const int o = sh_lds_index<L>(4 * i);
         const dns_v4f v = {lds[o], lds[o + 1], lds[o + 2], lds[o + 3]};
-#if DNS_PROJ_NT & 2
         __builtin_nontemporal_store(v, g4 + i);
-#else
-        g4[i] = v;
-#endif
     }
     for (int e = (n4 << 2) + threadIdx.x; e < nfloats; e += SH_STAGE_THREADS) gbase[e] = lds[sh_lds_index<L>(e)];
 }
@@ -459,7 +417,7 @@ struct FwdParams {
     dnsplat_scene s;
     dnsplat_camera c;
     dnsplat_proj_out o;
-    int blocks;          // blocks of 256 Gaussians (phase 2 walks them with fewer workgroups)
+    int blocks;          // blocks of 64 Gaussians (phase 2 walks them with fewer workgroups)
 };
 
 // PHASE (dnsplat_proj_out.phase): 0 = everything in one launch; 1 = geometry only (the SH colour channels of the records stay
@@ -470,7 +428,7 @@ template <int L, int PHASE = 0>
 __global__ __launch_bounds__(SH_STAGE_THREADS) void project_fwd_kernel(FwdParams p)
 {
     __shared__ float sh_lds[(L == SH_DIRECT || PHASE == 1) ? 1 : SH_STAGE_THREADS * ShRowTraits<L>::LDS_ROW];
-    // PHASE 2 is launched with a FEW resident workgroups that walk the blocks of 256 Gaussians (p.blocks of them): it is meant to
+    // PHASE 2 is launched with a FEW resident workgroups that walk the blocks of 64 Gaussians (p.blocks of them): it is meant to
     // run beside other kernels and must leave them most of the wave slots.  The other phases: one block per workgroup.
     // The per-block work as a lambda: PHASE 2 calls it in a loop, the others exactly once — written as a loop for all of them, LLVM kept
     // every loop-invariant of the body (the staging's per-lane row indices and LDS addresses: ~70 VGPRs) live across the projection.
@@ -493,7 +451,7 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) void project_fwd_kernel(FwdParams
     // VISIBLE_ROWS (one-launch kernel, staged layouts): the lane projects its Gaussian FIRST and only the coefficient rows of the
     // Gaussians that survive the culling are staged — a dependent round trip (parameters, then rows) that the other waves of the CU
     // cover, for 28 % fewer row bytes on the benchmark scenes.
-    constexpr bool VISIBLE_ROWS = DNS_PROJ_VISIBLE_ROWS && PHASE == 0 && L != SH_DIRECT && SH_STAGE_THREADS == DNS_WAVE;
+    constexpr bool VISIBLE_ROWS = PHASE == 0 && L != SH_DIRECT;
     Cam cam_pre;
     Proj st_pre;
     float sc_pre[3] = {0.f, 0.f, 0.f};
@@ -521,7 +479,7 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) void project_fwd_kernel(FwdParams
     // STAGED: the 64-byte records of the workgroup's Gaussians leave through LDS as one coalesced stream (the coefficient rows are
     // dead by then) instead of four 16-byte pieces per lane at a 64-byte stride, which is 4x the write requests for the same lines.
     // Every lane has to reach that store, so the per-Gaussian work sits in a do { } while (false) whose `break`s replace the early returns.
-    constexpr bool STAGED = DNS_PROJ_STAGED_REC && PHASE == 0 && L != SH_DIRECT && SH_STAGE_THREADS == DNS_WAVE;
+    constexpr bool STAGED = PHASE == 0 && L != SH_DIRECT;
     float r[DNS_REC];
 #pragma unroll
     for (int i = 0; i < DNS_REC; ++i) r[i] = 0.f;
@@ -722,11 +680,7 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) void project_fwd_kernel(FwdParams
             const int q = k * SH_STAGE_THREADS + (int)threadIdx.x;
             const dns_v4f v = reinterpret_cast<const dns_v4f *>(sh_lds)[(q >> 2) * 5 + (q & 3)];
             if (q < pieces && (!skip_culled || ((rec_rows >> (q >> 2)) & 1ull))) {
-#if DNS_PROJ_NT & 2
                 __builtin_nontemporal_store(v, out + q);
-#else
-                out[q] = v;
-#endif
             }
         }
     }
@@ -808,31 +762,23 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC_T(POSE) void pro
     // Row-selective staging (see sh_stage_in_rows): only the coefficient rows of the visible Gaussians are read, and — with
     // dnsplat_proj_grads.sh_zero_state — the zero gradient rows of Gaussians that were culled before and are culled again are not
     // written a second time.  One 64-bit word per workgroup (a wave) on each side.
-    constexpr bool VISIBLE_ROWS = DNS_PROJ_VISIBLE_ROWS && L != SH_DIRECT && SH_STAGE_THREADS == DNS_WAVE;
-    // DNS_PROJ_BWD_ROWS_IN: 1 = READ only the visible Gaussians' coefficient rows (the staging then waits for the radii: a dependent
-    // round trip), 0 = the whole span is requested together with the radii, as before round 6.  Measured inside whole bench runs
-    // (profiles/r06_ab_per_gaussian.txt): at 2 waves / SIMD the round trip costs more than the bytes save (+5 %), at 3 waves it pays
-    // (C5: 0.474 -> 0.451 ms).
-#ifndef DNS_PROJ_BWD_ROWS_IN
-#define DNS_PROJ_BWD_ROWS_IN 1
-#endif
+    constexpr bool VISIBLE_ROWS = L != SH_DIRECT;
+    // Only the visible Gaussians' coefficient rows are READ (the staging then waits for the radii: a dependent round trip), not the
+    // whole span together with the radii as before round 6.  Measured inside whole bench runs (profiles/r06_ab_per_gaussian.txt): at
+    // 2 waves / SIMD the round trip costs more than the bytes save (+5 %), at 3 waves it pays (C5: 0.474 -> 0.451 ms).
     const uint64_t vis_rows = __ballot(g < p.s.N && radius_g > 0);
     uint64_t zero_known = 0ull;
-    const bool track_zero = SH_STAGE_THREADS == DNS_WAVE && p.g.sh_zero_state != nullptr && !sh_elsewhere && p.s.sh_degree >= 0;
+    const bool track_zero = p.g.sh_zero_state != nullptr && !sh_elsewhere && p.s.sh_degree >= 0;
     if (track_zero) zero_known = p.g.sh_zero_state[blockIdx.x];
-#ifndef DNS_PROJ_ZERO_ROWS
-#define DNS_PROJ_ZERO_ROWS 0
-#endif
     // every row of the workgroup is culled now and zero in memory already (wave-uniform): nothing of it needs writing
     const bool wg_stays_zero = track_zero && (vis_rows | ~zero_known) == 0ull;
-    // DNS_PROJ_ZERO_ROWS = 1 (round 6, first form): rows skipped one by one — the workgroup's one streaming store becomes 16-byte
-    // pieces with holes (partial lines) and the kernel gets 5-10 % SLOWER for 10 % fewer bytes (profiles/r06_ab_per_gaussian.txt).
-    // 0: all or nothing per workgroup.  In a random row order every 64 rows hold a visible one and nothing is ever skipped; along a
-    // Morton curve (densify.spatial_order) a camera's culled Gaussians are whole workgroups.
-    const bool my_row_stays_zero = DNS_PROJ_ZERO_ROWS ? (((zero_known & ~vis_rows) >> threadIdx.x) & 1ull) != 0ull : wg_stays_zero;
+    // All or nothing per workgroup.  Rows skipped one by one (round 6, first form) turned the workgroup's one streaming store into
+    // 16-byte pieces with holes (partial lines) and the kernel got 5-10 % SLOWER for 10 % fewer bytes (profiles/r06_ab_per_gaussian.txt).
+    // In a random row order every 64 rows hold a visible one and nothing is ever skipped; along a Morton curve (densify.spatial_order)
+    // a camera's culled Gaussians are whole workgroups.
     if (L != SH_DIRECT) {
         const float *base = (L == SH_CAT ? p.s.sh0 : p.s.shN) + (size_t)g0 * ShRowTraits<L>::ROW;
-        if (VISIBLE_ROWS && DNS_PROJ_BWD_ROWS_IN) sh_stage_in_rows<L>(base, nG * ShRowTraits<L>::ROW, sh_lds, vis_rows);
+        if (VISIBLE_ROWS) sh_stage_in_rows<L>(base, nG * ShRowTraits<L>::ROW, sh_lds, vis_rows);
         else sh_stage_in<L>(base, nG * ShRowTraits<L>::ROW, sh_lds);
         __syncthreads();
     }
@@ -873,9 +819,9 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC_T(POSE) void pro
 
     if (!ok) {
         if (L == SH_CAT) { lrow[0] = 0.f; lrow[1] = 0.f; lrow[2] = 0.f; }
-        else if (vsh0 && !sh_elsewhere && !my_row_stays_zero) { vsh0[0] = 0.f; vsh0[1] = 0.f; vsh0[2] = 0.f; }
+        else if (vsh0 && !sh_elsewhere && !wg_stays_zero) { vsh0[0] = 0.f; vsh0[1] = 0.f; vsh0[2] = 0.f; }
         if (L != SH_DIRECT) { for (int k = 0; k < 45; ++k) lN[k] = 0.f; }
-        else if (vshN && !sh_elsewhere && !my_row_stays_zero) for (int k = 0; k < 3 * restK; ++k) vshN[k] = 0.f;
+        else if (vshN && !sh_elsewhere && !wg_stays_zero) for (int k = 0; k < 3 * restK; ++k) vshN[k] = 0.f;
         if (p.g.v_colors) for (int k = 0; k < p.s.n_colors; ++k) p.g.v_colors[(size_t)g * p.s.n_colors + k] = 0.f;
     } else {
         float vr[DNS_REC];
@@ -1181,8 +1127,7 @@ __global__ __launch_bounds__(SH_STAGE_THREADS) DNS_PROJ_BWD_OCC_T(POSE) void pro
         __syncthreads();
         float *base = (L == SH_CAT ? p.g.v_sh0 : p.g.v_shN) + (size_t)g0 * ShRowTraits<L>::ROW;
         // rows to store: the visible ones and the culled ones whose memory is not known to be zero (see wg_stays_zero)
-        if (VISIBLE_ROWS && track_zero && DNS_PROJ_ZERO_ROWS) sh_stage_out_rows<L>(base, nG * ShRowTraits<L>::ROW, sh_lds, vis_rows | ~zero_known);
-        else if (VISIBLE_ROWS && wg_stays_zero) { /* nothing */ }
+        if (VISIBLE_ROWS && wg_stays_zero) { /* nothing */ }
         else sh_stage_out<L>(base, nG * ShRowTraits<L>::ROW, sh_lds);
     }
     // what memory holds now: zero rows exactly where the Gaussian is culled (lanes beyond N: bits unused)
@@ -1458,6 +1403,35 @@ static int sh_layout(const dnsplat_scene *s, const float *b0, int s0, const floa
     return SH_DIRECT;
 }
 
+// Launches a kernel template's instantiation for a coefficient layout (sh_layout).  The three are named in the order the launch sites
+// always named them: it decides the kernels' order in the code object.
+template <typename Kernel, typename... Args>
+static void launch_for_layout(int layout, Kernel split, Kernel cat, Kernel direct, dim3 grid, dim3 block, dnsplat_stream_t stream,
+                              const Args &...args)
+{
+    const Kernel kernel = layout == SH_SPLIT ? split : layout == SH_CAT ? cat : direct;
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, args...);
+}
+
+// the layout the projection backward runs in: the staged kernels need the gradient tensors in the same layout as the coefficients
+static int sh_layout_bwd(const dnsplat_scene *scene, const dnsplat_proj_grads *grads)
+{
+    const int layout = sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride);
+    if (layout != SH_DIRECT && layout != sh_layout(scene, grads->v_sh0, grads->v_sh0_stride, grads->v_shN, grads->v_shN_stride))
+        return SH_DIRECT;
+    return layout;
+}
+
+// what dnsplat_project_bwd and dnsplat_project_bwd_pose ask of their arguments for N > 0
+static int check_bwd(const dnsplat_scene *scene, const dnsplat_camera *cam, const dnsplat_proj_out *fwd, const dnsplat_proj_grads *grads)
+{
+    if (!grads->radii || !grads->v_splats || !grads->v_means || !grads->v_quats || !grads->v_scales || !grads->v_opacities)
+        return DNSPLAT_ERR_INVALID_ARG;
+    if (scene->sh_degree > 3) return DNSPLAT_ERR_UNSUPPORTED;
+    if (fwd->with_normal_channels && !cam->normal_frame) return DNSPLAT_ERR_INVALID_ARG;
+    return DNSPLAT_OK;
+}
+
 static int check_scene(const dnsplat_scene *s, const dnsplat_camera *c, const dnsplat_proj_out *o)
 {
     if (!s || !c || !o) return DNSPLAT_ERR_INVALID_ARG;
@@ -1484,6 +1458,10 @@ static int check_scene(const dnsplat_scene *s, const dnsplat_camera *c, const dn
     return DNSPLAT_OK;
 }
 
+// Resident workgroups of the colour half of the two-phase forward (phase 2), which runs beside the binning and must leave it most of the
+// wave slots.
+constexpr int COLOUR_WGS = 512;
+
 extern "C" int dnsplat_project_fwd(const dnsplat_scene *scene, const dnsplat_camera *cam,
                                    const dnsplat_proj_out *out, dnsplat_stream_t stream)
 {
@@ -1497,22 +1475,15 @@ extern "C" int dnsplat_project_fwd(const dnsplat_scene *scene, const dnsplat_cam
     FwdParams p{*scene, *cam, *out, (scene->N + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS};
     dim3 block(SH_STAGE_THREADS), grid((scene->N + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS);
     if (out->phase < 0 || out->phase > 2 || (out->phase != 0 && scene->sh_degree < 0)) return DNSPLAT_ERR_INVALID_ARG;
+    const int layout = sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride);
     if (out->phase == 1) {
         hipLaunchKernelGGL((project_fwd_kernel<SH_DIRECT, 1>), grid, block, 0, (hipStream_t)stream, p);
     } else if (out->phase == 2) {
-        const char *e = getenv("DNSPLAT_COLOUR_WGS");
-        grid = dim3(min((int)grid.x, e ? atoi(e) : 512));
-        switch (sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride)) {
-            case SH_SPLIT: hipLaunchKernelGGL((project_fwd_kernel<SH_SPLIT, 2>), grid, block, 0, (hipStream_t)stream, p); break;
-            case SH_CAT: hipLaunchKernelGGL((project_fwd_kernel<SH_CAT, 2>), grid, block, 0, (hipStream_t)stream, p); break;
-            default: hipLaunchKernelGGL((project_fwd_kernel<SH_DIRECT, 2>), grid, block, 0, (hipStream_t)stream, p);
-        }
+        grid = dim3(min((int)grid.x, COLOUR_WGS));
+        launch_for_layout(layout, project_fwd_kernel<SH_SPLIT, 2>, project_fwd_kernel<SH_CAT, 2>, project_fwd_kernel<SH_DIRECT, 2>, grid, block,
+                          stream, p);
     } else {
-        switch (sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride)) {
-            case SH_SPLIT: hipLaunchKernelGGL(project_fwd_kernel<SH_SPLIT>, grid, block, 0, (hipStream_t)stream, p); break;
-            case SH_CAT: hipLaunchKernelGGL(project_fwd_kernel<SH_CAT>, grid, block, 0, (hipStream_t)stream, p); break;
-            default: hipLaunchKernelGGL(project_fwd_kernel<SH_DIRECT>, grid, block, 0, (hipStream_t)stream, p);
-        }
+        launch_for_layout(layout, project_fwd_kernel<SH_SPLIT>, project_fwd_kernel<SH_CAT>, project_fwd_kernel<SH_DIRECT>, grid, block, stream, p);
     }
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
@@ -1524,22 +1495,12 @@ extern "C" int dnsplat_project_bwd(const dnsplat_scene *scene, const dnsplat_cam
 {
     if (!scene || !cam || !fwd || !grads) return DNSPLAT_ERR_INVALID_ARG;
     if (scene->N == 0) return DNSPLAT_OK;
-    if (!grads->radii || !grads->v_splats || !grads->v_means || !grads->v_quats || !grads->v_scales ||
-        !grads->v_opacities)
-        return DNSPLAT_ERR_INVALID_ARG;
-    if (scene->sh_degree > 3) return DNSPLAT_ERR_UNSUPPORTED;
-    if (fwd->with_normal_channels && !cam->normal_frame) return DNSPLAT_ERR_INVALID_ARG;
+    const int rc = check_bwd(scene, cam, fwd, grads);
+    if (rc != DNSPLAT_OK) return rc;
     BwdParams p{*scene, *cam, *fwd, *grads};
     dim3 block(SH_STAGE_THREADS), grid((scene->N + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS);
-    // the staged kernels need the gradient tensors in the same layout as the coefficients
-    int layout = sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride);
-    if (layout != SH_DIRECT && layout != sh_layout(scene, grads->v_sh0, grads->v_sh0_stride, grads->v_shN, grads->v_shN_stride))
-        layout = SH_DIRECT;
-    switch (layout) {
-        case SH_SPLIT: hipLaunchKernelGGL(project_bwd_kernel<SH_SPLIT>, grid, block, 0, (hipStream_t)stream, p); break;
-        case SH_CAT: hipLaunchKernelGGL(project_bwd_kernel<SH_CAT>, grid, block, 0, (hipStream_t)stream, p); break;
-        default: hipLaunchKernelGGL(project_bwd_kernel<SH_DIRECT>, grid, block, 0, (hipStream_t)stream, p);
-    }
+    launch_for_layout(sh_layout_bwd(scene, grads), project_bwd_kernel<SH_SPLIT>, project_bwd_kernel<SH_CAT>, project_bwd_kernel<SH_DIRECT>, grid,
+                      block, stream, p);
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
 }
@@ -1562,22 +1523,14 @@ extern "C" int dnsplat_project_bwd_pose(const dnsplat_scene *scene, const dnspla
     const int n_chunks = (nb + POSE_CHUNK - 1) / POSE_CHUNK;
     double *sums = reinterpret_cast<double *>(pose->partials + (size_t)nb * 16);
     if (scene->N > 0) {
-        if (!grads->radii || !grads->v_splats || !grads->v_means || !grads->v_quats || !grads->v_scales || !grads->v_opacities ||
-            !cam->K)
-            return DNSPLAT_ERR_INVALID_ARG;
-        if (scene->sh_degree > 3) return DNSPLAT_ERR_UNSUPPORTED;
-        if (fwd->with_normal_channels && !cam->normal_frame) return DNSPLAT_ERR_INVALID_ARG;
+        if (!cam->K) return DNSPLAT_ERR_INVALID_ARG;
+        const int rc = check_bwd(scene, cam, fwd, grads);
+        if (rc != DNSPLAT_OK) return rc;
         BwdPoseParams p;
         p.s = *scene; p.c = *cam; p.o = *fwd; p.g = *grads; p.pose_rows = pose->partials;
         dim3 block(SH_STAGE_THREADS), grid(nb);
-        int layout = sh_layout(scene, scene->sh0, scene->sh0_stride, scene->shN, scene->shN_stride);
-        if (layout != SH_DIRECT && layout != sh_layout(scene, grads->v_sh0, grads->v_sh0_stride, grads->v_shN, grads->v_shN_stride))
-            layout = SH_DIRECT;
-        switch (layout) {
-            case SH_SPLIT: hipLaunchKernelGGL((project_bwd_kernel<SH_SPLIT, true>), grid, block, 0, (hipStream_t)stream, p); break;
-            case SH_CAT: hipLaunchKernelGGL((project_bwd_kernel<SH_CAT, true>), grid, block, 0, (hipStream_t)stream, p); break;
-            default: hipLaunchKernelGGL((project_bwd_kernel<SH_DIRECT, true>), grid, block, 0, (hipStream_t)stream, p);
-        }
+        launch_for_layout(sh_layout_bwd(scene, grads), project_bwd_kernel<SH_SPLIT, true>, project_bwd_kernel<SH_CAT, true>,
+                          project_bwd_kernel<SH_DIRECT, true>, grid, block, stream, p);
         DNS_CHECK_LAUNCH();
         hipLaunchKernelGGL(pose_reduce_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, nb, pose->partials, sums);
         DNS_CHECK_LAUNCH();
@@ -1650,19 +1603,9 @@ static int launch_sh_from_factors(int32_t N, int32_t n_views, int32_t skip_view,
     dim3 block(SH_STAGE_THREADS), grid((N + SH_STAGE_THREADS - 1) / SH_STAGE_THREADS);
     const int restK = sh_K - 1;
     const int skip = ADD ? skip_view : -1;
-    switch (layout) {
-        case SH_SPLIT:
-            hipLaunchKernelGGL((sh_from_factors_kernel<SH_SPLIT, PACKED, ADD>), grid, block, 0, (hipStream_t)stream, N, n_views, skip, factors,
-                               slab_words, means, sh_degree, scale, v_sh0, v_sh0_stride, v_shN, v_shN_stride, restK);
-            break;
-        case SH_CAT:
-            hipLaunchKernelGGL((sh_from_factors_kernel<SH_CAT, PACKED, ADD>), grid, block, 0, (hipStream_t)stream, N, n_views, skip, factors,
-                               slab_words, means, sh_degree, scale, v_sh0, v_sh0_stride, v_shN, v_shN_stride, restK);
-            break;
-        default:
-            hipLaunchKernelGGL((sh_from_factors_kernel<SH_DIRECT, PACKED, ADD>), grid, block, 0, (hipStream_t)stream, N, n_views, skip, factors,
-                               slab_words, means, sh_degree, scale, v_sh0, v_sh0_stride, v_shN, v_shN_stride, restK);
-    }
+    launch_for_layout(layout, sh_from_factors_kernel<SH_SPLIT, PACKED, ADD>, sh_from_factors_kernel<SH_CAT, PACKED, ADD>,
+                      sh_from_factors_kernel<SH_DIRECT, PACKED, ADD>, grid, block, stream, N, n_views, skip, factors, slab_words, means, sh_degree,
+                      scale, v_sh0, v_sh0_stride, v_shN, v_shN_stride, restK);
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
 }

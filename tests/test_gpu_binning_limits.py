@@ -6,7 +6,8 @@ The binning picks its route from the frame: uint16 tile keys and two LSD tile pa
 uint32 keys and three passes beyond; the fp32-reciprocal row division of the pair generator only with <= 256 tile columns and
 <= 65536 tiles (g.exact); the `all` term of the range histogram when a box row spans >= 2^dbits tiles of the first pass's digit;
 capped scan segments (8 segments of more than 2048 chunk counters) beyond 2^26 pairs; chunks of 4096 pairs that belong to a
-single Gaussian; 4096-key depth-sort chunks from 2^22 Gaussians on; 1 to 4 radix passes of the deterministic gradient reduction.
+single Gaussian; 4096-key depth-sort chunks from 2^22 Gaussians on; 1 to 4 radix passes of the deterministic gradient reduction; one
+tile pass that is first and last at once, at every digit width, up to 256 tiles.
 Every test asserts that its frame reached the regime it is about and prints the figures ("[binning] ..." lines).
 
 Scenes are given in camera space (camera at the origin looking down +z, viewmat = identity): a Gaussian is placed by its pixel
@@ -534,3 +535,18 @@ def test_deterministic_reduction_beyond_2_pow_24_records(dns, orc, deterministic
     rec, n = _det_case(dns, orc, monkeypatch, inp, vms, Ks, W, H, seed=24, what="4 x 4.5 M records", sh_degree=0)
     assert rec == C * N > 1 << 24 and n > 0
     assert (_tile_bits(rec) + 7) // 8 == 4
+
+
+# ------------------------------------------------------------------------------------------------
+# 13. single-pass tile sorts: 2 ... 256 tiles, ONE pass that is the first (generates the pairs) and the last (no key store, tile offsets)
+# at once, over every digit width 1 ... 8
+
+@pytest.mark.parametrize("W,H", [(32, 16), (32, 32), (64, 32), (64, 64), (128, 64), (128, 128), (256, 128), (256, 256)])
+def test_single_pass_tile_sort_at_every_digit_width(dns, orc, W, H):
+    oracle_threads()
+    T = (W // 16) * (H // 16)
+    bits = T.bit_length() - 1                      # T is a power of two: 1 ... 8 bits
+    inp, _gp, viewmat, K, _cam = _scene(*_clutter(300, W, H, seed=bits, smin=0.5, smax=max(W, H) / 4.0), W, H, float(W), seed=bits)
+    fig = _dropin_ints(dns, orc, inp, viewmat, K, W, H, f"{W}x{H}, {T} tiles")
+    assert fig["tiles"] == T and fig["passes"] == 1 and fig["dbits"] == [bits] and fig["key"] == 16 and fig["exact"]
+    assert fig["pairs"] > 0 and fig["max_tiles"] > 1

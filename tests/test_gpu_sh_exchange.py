@@ -22,7 +22,7 @@ DEV = "cuda"
 U24 = 2.0 ** -24
 
 WAVE = 64                       # splat_common.h DNS_WAVE: Gaussians per mask word
-STAGE_THREADS = 64              # project.hip SH_STAGE_THREADS = DNS_PROJ_THREADS: Gaussians per workgroup of the rebuild kernels
+STAGE_THREADS = 64              # project.hip SH_STAGE_THREADS = DNS_WAVE: Gaussians per workgroup of the rebuild kernels
 REC_CH0 = 6                     # splat_common.h: the first colour channel of a record
 REC = 16                        # include/dnsplat.h DNSPLAT_RECORD_FLOATS
 SCAN_THREADS = 1024             # project.hip VIS_SCAN_THREADS: visible_scan_kernel's one workgroup
@@ -108,7 +108,7 @@ def test_constants_are_the_kernels(dns):
 
     assert int(rhs(common, "DNS_WAVE")) == WAVE and int(rhs(common, "REC_CH0")) == REC_CH0
     assert rhs(common, "DNS_REC") == "DNSPLAT_RECORD_FLOATS" and int(rhs(header, "DNSPLAT_RECORD_FLOATS")) == REC
-    assert rhs(project, "SH_STAGE_THREADS") == "DNS_PROJ_THREADS" and int(rhs(project, "DNS_PROJ_THREADS")) == STAGE_THREADS == WAVE
+    assert rhs(project, "SH_STAGE_THREADS") == "DNS_WAVE" and int(rhs(common, "DNS_WAVE")) == STAGE_THREADS == WAVE
     assert int(rhs(project, "VIS_SCAN_THREADS")) == SCAN_THREADS
     assert "__launch_bounds__(VIS_SCAN_THREADS) void visible_scan_kernel(" in project
     assert "hipLaunchKernelGGL(visible_scan_kernel, dim3(1), dim3(VIS_SCAN_THREADS)," in project
