@@ -39,6 +39,8 @@ from . import mesh_cull, torch_mesh_cull  # noqa: F401
 from .mesh_cull import cull_mesh, culled_mesh_metrics, cut_mesh, render_mesh_depth, vertex_visibility  # noqa: F401
 from . import tsdf, torch_tsdf  # noqa: F401
 from .tsdf import TSDFVolume, fuse_tsdf_mesh  # noqa: F401
+from . import mesh_clusters, torch_mesh_clusters  # noqa: F401
+from .mesh_clusters import cluster_connected_triangles, filter_small_clusters  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -53,5 +55,6 @@ __all__ = [
     "install_pd_metrics", "mesh_metrics", "sample_mesh_surface",
     "mesh_cull", "torch_mesh_cull", "cull_mesh", "culled_mesh_metrics", "cut_mesh", "render_mesh_depth", "vertex_visibility",
     "tsdf", "torch_tsdf", "TSDFVolume", "fuse_tsdf_mesh",
+    "mesh_clusters", "torch_mesh_clusters", "cluster_connected_triangles", "filter_small_clusters",
     "build_library", "load_library", "DnsplatError",
 ]

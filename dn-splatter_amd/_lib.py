@@ -257,6 +257,22 @@ class MeshCutArgs(ctypes.Structure):
     ]
 
 
+class MeshClustersArgs(ctypes.Structure):
+    _fields_ = [
+        ("V", c_int32), ("T", c_int32), ("triangles", c_void_p), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
+        ("labels", c_void_p), ("sizes", c_void_p), ("counts", c_void_p), ("status", c_void_p),
+    ]
+
+
+class MeshFilterArgs(ctypes.Structure):
+    _fields_ = [
+        ("V", c_int32), ("T", c_int32), ("triangles", c_void_p), ("labels", c_void_p), ("sizes", c_void_p), ("cluster_counts", c_void_p),
+        ("keep_largest", c_int32), ("min_triangles", c_int32), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
+        ("threshold", c_void_p), ("counts", c_void_p), ("cap_v", c_int64), ("cap_t", c_int64),
+        ("vertex_index", c_void_p), ("out_triangles", c_void_p), ("status", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -293,6 +309,9 @@ EXPORTS = [
     # likewise: TSDF fusion (frames into a volume, vertex colours) and marching cubes over the observed part of a lattice
     "dnsplat_tsdf_integrate", "dnsplat_tsdf_vertex_colors", "dnsplat_mc_observed_scratch_bytes", "dnsplat_mc_count_observed",
     "dnsplat_mc_emit_observed",
+    # likewise: the connected-component filter of a mesh (clusters of triangles, the small ones cut)
+    "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_clusters", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_mesh_filter_count",
+    "dnsplat_mesh_filter_emit",
 ]
 
 _lib = None
@@ -415,12 +434,20 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_mc_observed_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
         L.dnsplat_mc_count_observed.argtypes = [ctypes.POINTER(McObservedArgs), c_void_p]
         L.dnsplat_mc_emit_observed.argtypes = [ctypes.POINTER(McObservedArgs), c_void_p]
+        L.dnsplat_mesh_clusters_scratch_bytes.restype = c_size_t
+        L.dnsplat_mesh_clusters_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_mesh_clusters.argtypes = [ctypes.POINTER(MeshClustersArgs), c_void_p]
+        L.dnsplat_mesh_filter_scratch_bytes.restype = c_size_t
+        L.dnsplat_mesh_filter_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_mesh_filter_count.argtypes = [ctypes.POINTER(MeshFilterArgs), c_void_p]
+        L.dnsplat_mesh_filter_emit.argtypes = [ctypes.POINTER(MeshFilterArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
                             "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
                             "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
-                            "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes"):
+                            "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes",
+                            "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_filter_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshCutArgs, MeshDepthArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -502,6 +502,29 @@ def _mesh_cut_args(vertices, triangles, obs, invalid, obs_threshold, invalid_sha
     a.cap_v = 0 if out_vertices is None else out_vertices.shape[0]
     a.cap_t = 0 if out_triangles is None else out_triangles.shape[0]
     a.out_vertices, a.out_triangles, a.status = _ptr(out_vertices), _ptr(out_triangles), _ptr(status)
+    return a
+
+
+def _mesh_clusters_args(n_vertices, triangles, scratch, labels, sizes, counts, status):
+    a = MeshClustersArgs()
+    a.V, a.T = n_vertices, triangles.shape[0]
+    a.triangles = _ptr(triangles)
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.labels, a.sizes, a.counts, a.status = _ptr(labels), _ptr(sizes), _ptr(counts), _ptr(status)
+    return a
+
+
+def _mesh_filter_args(n_vertices, triangles, labels, sizes, cluster_counts, keep_largest, min_triangles, scratch, threshold, counts,
+                      vertex_index=None, out_triangles=None, status=None):
+    a = MeshFilterArgs()
+    a.V, a.T = n_vertices, triangles.shape[0]
+    a.triangles, a.labels, a.sizes, a.cluster_counts = _ptr(triangles), _ptr(labels), _ptr(sizes), _ptr(cluster_counts)
+    a.keep_largest, a.min_triangles = keep_largest, min_triangles
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.threshold, a.counts = _ptr(threshold), _ptr(counts)
+    a.cap_v = 0 if vertex_index is None else vertex_index.shape[0]
+    a.cap_t = 0 if out_triangles is None else out_triangles.shape[0]
+    a.vertex_index, a.out_triangles, a.status = _ptr(vertex_index), _ptr(out_triangles), _ptr(status)
     return a
 
 

@@ -15,17 +15,16 @@
 //   dnsplat_mesh_cut_count    hipMemset, mv_keep_kernel (the rule per triangle, marks of the referenced vertices, kept per block),
 //                             mv_mark_count_kernel (marked vertices per block), mv_cut_scan_kernel (both scans, counts = {V', T'})
 //   dnsplat_mesh_cut_emit     mv_emit_vertices_kernel (the vertices in order, mark -> new id), mv_emit_triangles_kernel
+// mv_mark_count_kernel, mv_cut_scan_kernel and mv_emit_triangles_kernel are in mesh_cut.h: meshclusters.hip ends its cut with them too.
 //
 // Positive floats order as their bit patterns and an integer minimum does not depend on the order of arrival: the depth map is a
 // canonical function of its inputs.  No floating-point atomic; the cut has no atomic at all (the scans, the flag rank and the layout
 // of the ordered append of block_scan.h; the marks are plain stores of the same value 1).
-#include "block_scan.h"
+#include "mesh_cut.h"
 
 namespace {
 
-constexpr int MV_THREADS = 256;
 constexpr int MV_SMALL = 16;               // boxes of up to this many pixels stay with their lane
-constexpr int MV_SCAN_PER = 4;             // mv_cut_scan_kernel: MV_THREADS * MV_SCAN_PER block counts per trip
 constexpr unsigned MV_INF_BITS = 0x7f800000u;
 
 struct MvDepth {
@@ -264,8 +263,6 @@ struct MvScratch {
     uint8_t *keep;
 };
 
-int mv_blocks(long long n) { return (int)((n + MV_THREADS - 1) / MV_THREADS); }
-
 size_t mv_cut_bytes(int V, int T)
 {
     return ((size_t)V + mv_blocks(T) + mv_blocks(V)) * sizeof(int32_t) + (size_t)T;
@@ -308,25 +305,6 @@ __global__ __launch_bounds__(MV_THREADS) void mv_keep_kernel(int V, int T, const
     if (threadIdx.x == 0) tcount[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(MV_THREADS) void mv_mark_count_kernel(int V, const int32_t *__restrict__ marks, int32_t *__restrict__ vcount)
-{
-    __shared__ int wave_tot[MV_THREADS / DNS_WAVE];
-    const int i = blockIdx.x * MV_THREADS + threadIdx.x;
-    int total;
-    dns_block_rank<MV_THREADS>(i < V && marks[i] != 0, wave_tot, total);
-    if (threadIdx.x == 0) vcount[blockIdx.x] = total;
-}
-
-// One workgroup: both arrays of block counts to their exclusive prefix sums in place; counts = {V', T'}
-__global__ __launch_bounds__(MV_THREADS) void mv_cut_scan_kernel(int nbv, int32_t *__restrict__ vcount, int nbt, int32_t *__restrict__ tcount,
-                                                                 int64_t *__restrict__ counts)
-{
-    const int nv = dns_scan_in_place<MV_THREADS, MV_SCAN_PER>(nbv, vcount);
-    __syncthreads();
-    const int nt = dns_scan_in_place<MV_THREADS, MV_SCAN_PER>(nbt, tcount);
-    if (threadIdx.x == 0) { counts[0] = nv; counts[1] = nt; }
-}
-
 __global__ __launch_bounds__(MV_THREADS) void mv_emit_vertices_kernel(int V, const float *__restrict__ vertices, const int32_t *__restrict__ vcount,
                                                                       int32_t *__restrict__ marks, long long cap_v, float *__restrict__ out)
 {
@@ -340,24 +318,6 @@ __global__ __launch_bounds__(MV_THREADS) void mv_emit_vertices_kernel(int V, con
     if (marked && id < cap_v) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) out[(size_t)id * 3 + k] = vertices[(size_t)i * 3 + k];
-    }
-}
-
-__global__ __launch_bounds__(MV_THREADS) void mv_emit_triangles_kernel(int T, const int32_t *__restrict__ triangles, const uint8_t *__restrict__ keep,
-                                                                       const int32_t *__restrict__ tcount, const int32_t *__restrict__ new_id,
-                                                                       const int64_t *__restrict__ counts, long long cap_v, long long cap_t,
-                                                                       int32_t *__restrict__ out, int32_t *__restrict__ status)
-{
-    __shared__ int wave_tot[MV_THREADS / DNS_WAVE];
-    const int t = blockIdx.x * MV_THREADS + threadIdx.x;
-    const bool kept = t < T && keep[t] != 0;
-    int total;
-    const int row = tcount[blockIdx.x] + dns_block_rank<MV_THREADS>(kept, wave_tot, total);
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        status[0] = (counts[0] > cap_v ? DNSPLAT_MESH_CUT_STATUS_VERTICES : 0) | (counts[1] > cap_t ? DNSPLAT_MESH_CUT_STATUS_TRIANGLES : 0);
-    if (kept && row < cap_t) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[(size_t)row * 3 + k] = new_id[triangles[(size_t)t * 3 + k]] - 1;
     }
 }
 

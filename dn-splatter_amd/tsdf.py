@@ -6,13 +6,15 @@ fuses them on the CPU with Open3D — a library a ROCm box does not have.  Here 
     frames) and ``extract_mesh`` (``dnsplat_mc_count_observed`` / ``dnsplat_mc_emit_observed`` — marching cubes over the voxels that
     were seen — and ``dnsplat_tsdf_vertex_colors``);
   * ``fuse_tsdf_mesh``: the exporter's loop (:961-1019) — render, mask, integrate ``batch`` frames per call, extract.  Its result feeds
-    ``mesh_cull.cull_mesh`` and ``geometry.mesh_metrics`` unchanged, so render -> fuse -> mesh -> cull -> score stays on the GPU.
+    ``mesh_cull.cull_mesh`` and ``geometry.mesh_metrics`` unchanged, so render -> fuse -> mesh -> cull -> score stays on the GPU;
+  * ``filter_clusters=`` of both: the exporter's last step (:1021-1039), Open3D's connected-component filter, through
+    ``mesh_clusters.filter_small_clusters``.
 
 The integration rule is restated from memory of Open3D's ``UniformTSDFVolume::Integrate``: IT IS THIS PROJECT'S DEFINITION, PARITY
 UNPINNED AGAINST Open3D.  ``torch_tsdf`` states it in PyTorch, and the kernels are held to that file with exact equality.  Poses are
 camera-to-world in the OpenGL convention, as ``mesh_cull`` takes them.
 
-Out of scope: Open3D's connected-component filter (:1021-1039), vdbfusion's space carving and its ``min_weight=5`` beyond the
+Out of scope: vdbfusion's space carving and its ``min_weight=5`` beyond the
 ``min_weight`` argument, sparse or hashed volumes (Open3D's ``ScalableTSDFVolume`` allocates blocks on demand; this volume is the box
 it is given), quadric decimation, PLY output, per-camera intrinsics within one call.  CPU tensors are refused; there is no CPU
 fallback."""
@@ -28,6 +30,7 @@ from torch import Tensor
 from . import _lib
 from ._ops import _f32c, _need_gpu, _ptr, _stream, _tsdf_args
 from .marching import MarchingBuffers, marching_cubes
+from .mesh_clusters import _filter_arguments, filter_small_clusters
 from .mesh_cull import _frame, _w2c
 from .torch_mesh_cull import intrinsics
 from .torch_tsdf import bounds_dims, ray_scale, world_vertices
@@ -110,17 +113,27 @@ class TSDFVolume:
         return out
 
     @torch.no_grad()
-    def extract_mesh(self, min_weight: float = 0.0, capacity: Optional[Tuple[int, int]] = None):
+    def extract_mesh(self, min_weight: float = 0.0, capacity: Optional[Tuple[int, int]] = None, filter_clusters=None):
         """The zero level of the volume over the voxels with ``weight > min_weight``: (vertices float64 [V,3] in world coordinates,
         ``origin + voxel_size * v`` in float64; triangles int32 [T,3]; colours float32 [V,3] in 0 ... 1, or None).  One host read of
         (V, T).  With ``capacity=(cap_v, cap_t)`` nothing is read: the three are full-capacity buffers and a fourth item is the
-        ``MarchingBuffers`` with the device counts and status (rows past the counts are unwritten)."""
+        ``MarchingBuffers`` with the device counts and status (rows past the counts are unwritten).
+        ``filter_clusters``: None (the default) returns the mesh as extracted; ``(keep_largest, min_triangles)`` — or True for the
+        reference's (50, 50) — applies ``mesh_clusters.filter_small_clusters`` to it (export_mesh.py:1021-1039), world vertices and
+        colours gathered; one more host read, of (V', T').  Not with ``capacity``: the filter needs the counts."""
         if min(self.dims) < 2:
             raise ValueError(f"a volume of {self.dims} has no cells")
+        filter_clusters = _filter_arguments(filter_clusters)
+        if filter_clusters is not None and capacity is not None:
+            raise ValueError("filter_clusters needs the counts of the mesh: extract without capacity")
         out = marching_cubes(self.tsdf, 0.0, capacity=capacity, weight=self.weight, min_weight=float(min_weight))
         vertices, triangles = (out.vertices, out.triangles) if capacity is not None else out
         colors = None if self.color is None else self.vertex_colors(vertices)
         world = world_vertices(vertices, self.origin, self.voxel_size)
+        if filter_clusters is not None:
+            if triangles.shape[0] == 0:
+                return world, triangles, colors
+            return filter_small_clusters((world, triangles, colors), *filter_clusters)
         return (world, triangles, colors, out) if isinstance(out, MarchingBuffers) else (world, triangles, colors)
 
 
@@ -131,11 +144,12 @@ def _same_intrinsics(a, b) -> bool:
 
 @torch.no_grad()
 def fuse_tsdf_mesh(renderer, cameras, bounds, voxel_size: float = 0.01, sdf_trunc: float = 0.03, depth_trunc: float = 20.0, masks=None,
-                   batch: int = 8, pixel_offset: float = 0.5, color: bool = True, min_weight: float = 0.0):
+                   batch: int = 8, pixel_offset: float = 0.5, color: bool = True, min_weight: float = 0.0, filter_clusters=None):
     """The loop of ``Open3DTSDFFusion.main`` (export_mesh.py:961-1019): every one of ``cameras`` rendered through
     ``renderer.get_outputs_batch`` under ``no_grad``, depth zeroed outside ``masks[f]`` if ``masks`` is given, ``batch`` frames fused
-    per ``integrate`` call into the volume of ``bounds`` = (lo, hi), then ``extract_mesh(min_weight)``.  The cameras share one set of
-    intrinsics.  Returns (vertices float64 [V,3] world, triangles int32 [T,3], colours float32 [V,3] or None) on the device — what
+    per ``integrate`` call into the volume of ``bounds`` = (lo, hi), then ``extract_mesh(min_weight, filter_clusters=filter_clusters)``:
+    ``filter_clusters=True`` is the exporter as written, with its connected-component filter (:1021-1039); None leaves the mesh raw.
+    The cameras share one set of intrinsics.  Returns (vertices float64 [V,3] world, triangles int32 [T,3], colours float32 [V,3] or None) on the device — what
     ``mesh_cull.cull_mesh`` and ``geometry.mesh_metrics`` take."""
     F_ = len(cameras)
     if F_ == 0:
@@ -163,4 +177,4 @@ def fuse_tsdf_mesh(renderer, cameras, bounds, voxel_size: float = 0.01, sdf_trun
         rgb = torch.stack([o["rgb"].detach() for o in outs]).float() if color else None
         poses = torch.stack([c.camera_to_worlds.detach().reshape(-1, 4)[:3] for c in chunk])
         volume.integrate(depth, rgb, poses, K)
-    return volume.extract_mesh(min_weight)
+    return volume.extract_mesh(min_weight, filter_clusters=filter_clusters)

@@ -6,7 +6,8 @@ Box-to-box and run-to-run drift (2-3 % on this pool) cancels; the minimum and me
     python tools/ab_kernels.py --entry dnsplat_raster_bwd --libs gpurun_ab/lib_base.so,gpurun_ab/lib_sym.so [--workload c2]
 
 ``--workload mc256`` / ``mc512``: instead of the frame, ``marching_cubes`` at level 0.5 on the density lattice of the C2 scene
-(tools/marching_time.py's), for ``--entry dnsplat_mc_count`` or ``dnsplat_mc_emit``.
+(tools/marching_time.py's), for ``--entry dnsplat_mc_count`` or ``dnsplat_mc_emit``; ``mc256cut`` / ``mc512cut``: ``cut_mesh`` on that
+mesh under seeded votes, for ``--entry dnsplat_mesh_cut_count`` or ``dnsplat_mesh_cut_emit``.
 """
 import argparse
 import ctypes
@@ -69,10 +70,21 @@ if args.workload.startswith("mc"):
 
     from dn_splatter_amd import marching  # noqa: E402
 
-    _, volume = marching_time.lattice(int(args.workload[2:]))
+    cut = args.workload.endswith("cut")    # mc256cut / mc512cut: cut_mesh on that mesh under seeded votes
+    _, volume = marching_time.lattice(int(args.workload[2:5]))
+    if cut:
+        from dn_splatter_amd import mesh_cull  # noqa: E402
+
+        vertices, triangles = marching.marching_cubes(volume, marching_time.LEVEL)
+        gen = torch.Generator(device=dev).manual_seed(2)
+        obs = torch.randint(0, 8, (vertices.shape[0],), device=dev, generator=gen, dtype=torch.int32)
+        invalid = torch.randint(0, 8, (vertices.shape[0],), device=dev, generator=gen, dtype=torch.int32)
     for it in range(2):
         armed = it == 1                    # first mesh: warm-up with the default library only
-        marching.marching_cubes(volume, marching_time.LEVEL)
+        if cut:
+            mesh_cull.cut_mesh(vertices, triangles, obs, invalid)
+        else:
+            marching.marching_cubes(volume, marching_time.LEVEL)
     torch.cuda.synchronize()
     for n, _ in libs:
         t = results[n]
