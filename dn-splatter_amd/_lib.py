@@ -71,6 +71,14 @@ class BinArgs(ctypes.Structure):
     ]
 
 
+class BinCells(ctypes.Structure):
+    _fields_ = [("shift_x", c_int32), ("shift_y", c_int32), ("n_tile_pairs", c_void_p), ("n_tile_pairs_max", c_void_p)]
+
+
+class RasterCells(ctypes.Structure):
+    _fields_ = [("shift_x", c_int32), ("shift_y", c_int32), ("tile_boxes", c_void_p)]
+
+
 class DnPost(ctypes.Structure):
     _fields_ = [
         ("background_rgb", c_void_p), ("rgb", c_void_p), ("depth", c_void_p), ("normal", c_void_p),
@@ -312,6 +320,9 @@ EXPORTS = [
     # likewise: the connected-component filter of a mesh (clusters of triangles, the small ones cut)
     "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_clusters", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_mesh_filter_count",
     "dnsplat_mesh_filter_emit",
+    # likewise: the fused path's tile lists per cell of several tiles
+    "dnsplat_bin_prepare_cells", "dnsplat_bin_emit_sort_cells", "dnsplat_raster_fwd_cells", "dnsplat_raster_bwd_cells",
+    "dnsplat_det_reduce_planes",
 ]
 
 _lib = None
@@ -361,6 +372,11 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_det_workspace_bytes.restype = c_size_t
         L.dnsplat_det_workspace_bytes.argtypes = [c_int64]
         L.dnsplat_det_reduce.argtypes = [ctypes.POINTER(DetArgs), c_void_p]
+        L.dnsplat_bin_prepare_cells.argtypes = [ctypes.POINTER(BinArgs), ctypes.POINTER(BinCells), c_void_p]
+        L.dnsplat_bin_emit_sort_cells.argtypes = [ctypes.POINTER(BinArgs), ctypes.POINTER(BinCells), c_void_p]
+        L.dnsplat_raster_fwd_cells.argtypes = [ctypes.POINTER(RasterArgs), ctypes.POINTER(RasterCells), c_void_p]
+        L.dnsplat_raster_bwd_cells.argtypes = [ctypes.POINTER(RasterArgs), ctypes.POINTER(RasterCells), c_void_p]
+        L.dnsplat_det_reduce_planes.argtypes = [ctypes.POINTER(DetArgs), c_int32, c_void_p]
         L.dnsplat_dn_depth_normals.argtypes = [c_int32, c_int32, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p]
         L.dnsplat_densify_stats.argtypes = [c_int32, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]

@@ -20,7 +20,7 @@ import ctypes
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -93,6 +93,13 @@ class _Buffers:
         self.static_cap: Dict[tuple, int] = {}
         self.n_max: Dict[tuple, Tensor] = {}     # "static" bin policy: running maximum of n_isects per (device, stream) + frame size key
         self.capacity_hint: Dict[tuple, int] = {}
+        # Frames binned over list cells (BIN_CELL) keep a second set of the same records, in (cell, Gaussian) pairs and keyed by the frame
+        # size key + the cell shifts: their buffers are sized by these.  The records above stay what they are for every reader —
+        # per-tile pair counts, which such a frame reports as well — and bound the cell capacities from above (a cell list is never
+        # longer than the tile lists it replaces).
+        self.cell_hint: Dict[tuple, int] = {}
+        self.static_cap_cells: Dict[tuple, int] = {}
+        self.n_max_cells: Dict[tuple, Tensor] = {}
 
     @staticmethod
     def _key(device):
@@ -123,7 +130,8 @@ class _Buffers:
         key = self._key(device)
         cur = self.pinned.get(key)
         if cur is None:
-            cur = torch.zeros(1, dtype=torch.int64).pin_memory()
+            # two words: a frame binned over list cells reports (cell pairs, tile pairs), every other frame fills the first only
+            cur = torch.zeros(2, dtype=torch.int64).pin_memory()
             self.pinned[key] = cur
         return cur
 
@@ -135,12 +143,12 @@ class _Buffers:
         key = self._key(device)
         ring = self.ring.get(key)
         if ring is None:
-            mem = torch.zeros(self.RING, dtype=torch.int64).pin_memory()
+            mem = torch.zeros(2 * self.RING, dtype=torch.int64).pin_memory()      # two words per slot, as pinned_i64
             ring = {"mem": mem, "events": [torch.cuda.Event() for _ in range(self.RING)], "next": 0, "pending": []}
             self.ring[key] = ring
         i = ring["next"]
         ring["next"] = (i + 1) % self.RING
-        slot = ring["mem"][i:i + 1]
+        slot = ring["mem"][2 * i:2 * i + 2]
         # the slot about to be reused must have been looked at — whoever owns it, also when counts were resolved out of order
         # through Binning.n_isects — and at most RING - 1 frames are ever unverified
         for p in [p for p in ring["pending"] if p.slot.data_ptr() == slot.data_ptr()]:
@@ -207,12 +215,30 @@ def set_bin_policy(mode: str) -> None:
     BIN_POLICY["mode"] = mode
 
 
+def _capacity_guess(key, cells) -> int:
+    """What earlier frames of this size say the lists of the next one need: per-tile pairs, or with list cells (cell, Gaussian) pairs
+    — never more than the per-tile guess, and nothing once that one has been forgotten."""
+    hint = BUFFERS.capacity_hint.get(key, 0)
+    if cells is None or not hint:
+        return hint
+    return min(hint, BUFFERS.cell_hint.get(key + cells, hint))
+
+
+def _learn_capacity(key, cells, n: int, n_tile: int) -> None:
+    """A frame's counts have reached the host: the guesses grow to 1.25 x what it needed."""
+    BUFFERS.capacity_hint[key] = max(BUFFERS.capacity_hint.get(key, 0), int(n_tile * 1.25) + 4096)
+    if cells is not None:
+        BUFFERS.cell_hint[key + cells] = max(BUFFERS.cell_hint.get(key + cells, 0), int(n * 1.25) + 4096)
+
+
 class _PendingCount:
     """The intersection count of one frame binned under the "deferred" policy, until the host has looked at it."""
 
-    def __init__(self, ring, slot, event, capacity, key):
+    def __init__(self, ring, slot, event, capacity, key, cells=None):
         self.ring, self.slot, self.event, self.capacity, self.key = ring, slot, event, capacity, key
         self.n: Optional[int] = None
+        self.cells = cells              # list cells: n / capacity are (cell, Gaussian) pairs and n_tile the per-tile pair count
+        self.n_tile: Optional[int] = None
         self.overflowed = False
 
     def ready(self) -> bool:
@@ -223,11 +249,11 @@ class _PendingCount:
         that overflowed (its lists are truncated: nobody may read its count or its list as if it were complete)."""
         if self.n is None:
             self.event.synchronize()
-            self.n = int(self.slot.item())
+            self.n = int(self.slot[0])
+            self.n_tile = int(self.slot[1]) if self.cells else self.n
             if self in self.ring["pending"]:
                 self.ring["pending"].remove(self)
-            hint = BUFFERS.capacity_hint.get(self.key, 0)
-            BUFFERS.capacity_hint[self.key] = max(hint, int(self.n * 1.25) + 4096)
+            _learn_capacity(self.key, self.cells, self.n, self.n_tile)
             self.overflowed = self.n > self.capacity
         if self.overflowed:
             raise _lib.DnsplatError(
@@ -250,12 +276,20 @@ def static_overflow(device, stream=None) -> Optional[int]:
         if k[:2] != skey:
             continue
         n = int(t.item())
-        if n > BUFFERS.static_cap.get(k, 0):
+        # frames binned over list cells: their buffers hold (cell, Gaussian) pairs, counted and bounded beside the per-tile figures
+        over_cells = [(ck, int(ct.item())) for ck, ct in BUFFERS.n_max_cells.items() if ck[:len(k)] == k]
+        over_cells = [(ck, nc) for ck, nc in over_cells if nc > BUFFERS.static_cap_cells.get(ck, 0)]
+        if n > BUFFERS.static_cap.get(k, 0) or over_cells:
             worst = n if worst is None else max(worst, n)
             hkey = k[2:]                                   # (device, N, width, height): the key of the capacity guesses
             BUFFERS.capacity_hint[hkey] = max(BUFFERS.capacity_hint.get(hkey, 0), int(n * 1.25) + 4096)
             t.zero_()
             BUFFERS.static_cap.pop(k, None)
+            for ck, nc in over_cells:
+                BUFFERS.cell_hint[ck[2:]] = max(BUFFERS.cell_hint.get(ck[2:], 0), int(nc * 1.25) + 4096)
+            for ck in [ck for ck in BUFFERS.n_max_cells if ck[:len(k)] == k]:
+                BUFFERS.n_max_cells[ck].zero_()
+                BUFFERS.static_cap_cells.pop(ck, None)
     return worst
 
 
@@ -265,8 +299,9 @@ def forget_capacity_guesses(device=None) -> None:
     maxima, static capacities) are NOT touched: the running maximum is a device word that the captured bin kernels of a live
     graph.GraphedStep still write on every replay, and this dict holds the reference that keeps it allocated — they go
     with their step (GraphedStep.close -> forget_static)."""
-    for k in [k for k in BUFFERS.capacity_hint if device is None or k[0] == device]:
-        del BUFFERS.capacity_hint[k]
+    for d in (BUFFERS.capacity_hint, BUFFERS.cell_hint):
+        for k in [k for k in d if device is None or k[0] == device]:
+            del d[k]
 
 
 def carry_capacity_guesses(device, n_old: int, n_new: int, slack: float = 1.1) -> int:
@@ -275,14 +310,15 @@ def carry_capacity_guesses(device, n_old: int, n_new: int, slack: float = 1.1) -
     n_new / n_old x ``slack`` and file it under the new size.  A guess is a capacity, not a promise: a frame that outgrows it is
     reported by the bin policy in force (``GraphedStep.check()`` raises and enlarges it).  Returns the number of guesses carried."""
     carried = 0
-    for k in [k for k in BUFFERS.capacity_hint if (device is None or k[0] == device) and k[1] == n_old]:
-        hint = BUFFERS.capacity_hint.pop(k)
-        nk = (k[0], n_new) + tuple(k[2:])
-        # never scaled DOWN: culling removes low-opacity, small-footprint Gaussians, so the intersections fall less than N does, and
-        # an under-estimate would make the next capture's warm-up frame overflow instead of sizing itself (ADVICE r05)
-        ratio = max(1.0, n_new / max(n_old, 1))
-        BUFFERS.capacity_hint[nk] = max(BUFFERS.capacity_hint.get(nk, 0), int(hint * ratio * slack) + 4096)
-        carried += 1
+    for d in (BUFFERS.capacity_hint, BUFFERS.cell_hint):      # the cell-pair guesses travel with the per-tile ones, uncounted
+        for k in [k for k in d if (device is None or k[0] == device) and k[1] == n_old]:
+            hint = d.pop(k)
+            nk = (k[0], n_new) + tuple(k[2:])
+            # never scaled DOWN: culling removes low-opacity, small-footprint Gaussians, so the intersections fall less than N does, and
+            # an under-estimate would make the next capture's warm-up frame overflow instead of sizing itself (ADVICE r05)
+            ratio = max(1.0, n_new / max(n_old, 1))
+            d[nk] = max(d.get(nk, 0), int(hint * ratio * slack) + 4096)
+            carried += d is BUFFERS.capacity_hint
     return carried
 
 
@@ -290,7 +326,7 @@ def forget_static(device, stream) -> None:
     """Drops the "static" policy's per-stream records (running maxima, capacities) of ``stream``: called when the GraphedStep that
     owned the stream is discarded, so that they do not accumulate across re-captures."""
     skey = (device, stream.cuda_stream)
-    for d in (BUFFERS.n_max, BUFFERS.static_cap):
+    for d in (BUFFERS.n_max, BUFFERS.static_cap, BUFFERS.n_max_cells, BUFFERS.static_cap_cells):
         for k in [k for k in d if k[:2] == skey]:
             del d[k]
     for d in (BUFFERS.ws, BUFFERS.pinned, BUFFERS.ring, BUFFERS.side):
@@ -896,17 +932,35 @@ class Binning:
         self.tile_ends, self._n_dev = tile_ends, n_dev
         self._n, self.pending = n_isects, pending
         self.tile_width, self.tile_height, self.n_cameras = tile_width, tile_height, n_cameras
+        # List cells (bin_tiles(cells=)): the lists above are per cell of 2^sx x 2^sy tiles — list_width x list_height of them per
+        # camera — and n_isects counts (cell, Gaussian) pairs; the per-tile pair count travels beside it
+        self.cells: Optional[Tuple[int, int]] = None
+        self.list_width, self.list_height = tile_width, tile_height
+        self._n_tile, self._n_tile_dev = None, None
+        self.tile_boxes: Optional[Tensor] = None
+        self.keep: Optional[dict] = None      # fused pass: the forward's keep masks over these lists ("masks", "stride")
 
     @property
     def n_isects(self) -> int:
         if self.pending is not None:
             self._n = self.pending.resolve()      # raises (every time) if that frame overflowed: self.pending stays
+            self._n_tile = self.pending.n_tile
             self.pending = None
         if self._n is None:                      # "static" policy: nobody has asked yet — read the device scalar (synchronises)
             self._n = int(self._n_dev.item())
             if self._n > self.flatten_ids.numel():
                 raise _lib.DnsplatError(f"tile binning: {self._n} intersections exceed the static capacity {self.flatten_ids.numel()}")
         return self._n
+
+    @property
+    def n_tile_pairs(self) -> int:
+        """What n_isects would be with one list per tile (it is n_isects without list cells)."""
+        n = self.n_isects                        # waits for / verifies the frame's counts
+        if self.cells is None:
+            return n
+        if self._n_tile is None:
+            self._n_tile = int(self._n_tile_dev.item())
+        return self._n_tile
 
     def filled_offsets(self) -> Tensor:
         """gsplat's isect_offsets [C*T+1]: an empty tile carries the offset of the next non-empty one."""
@@ -926,19 +980,32 @@ class Binning:
 
 def bin_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tiles: Tensor, width: int, height: int,
               tile_size: int, after_emit=None, n_cameras: int = 1, tight_splats: Optional[Tensor] = None,
-              defer_ok: bool = False, want_ends: bool = False, tile_boxes: Optional[Tensor] = None) -> Binning:
+              defer_ok: bool = False, want_ends: bool = False, tile_boxes: Optional[Tensor] = None,
+              cells: Optional[Tuple[int, int]] = None, exact: Optional[int] = None) -> Binning:
     """Stage 2 over ``n_cameras`` stacked projections (inputs flattened to [C*N, ...]).  ``after_emit(binning)`` (optional)
     is called right after the emit/sort kernels are enqueued and BEFORE any host wait, so the caller can queue the
-    compositing kernel behind them; in "capacity" mode it is called again if the capacity guess turned out too small."""
+    compositing kernel behind them; in "capacity" mode it is called again if the capacity guess turned out too small.
+    ``cells`` = (shift_x, shift_y), with ``tile_boxes``: one list per cell of 2^shift_x x 2^shift_y tiles (dnsplat_bin_cells) — the
+    lists, their offsets, the count and every capacity are then in (cell, Gaussian) pairs, and the per-tile pair count is
+    ``Binning.n_tile_pairs``.  ``exact``: the count is known (a frame binned before): lists of exactly that size, no host wait,
+    no record of it kept."""
     lib = _lib.lib()
     dev = means2d.device
     N = radii.numel()
     tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-    T = tw * th * n_cameras
-    n_dev = torch.empty(1, dtype=torch.int64, device=dev)
+    if cells is not None and cells == (0, 0):
+        cells = None
+    lw, lh = (tw, th) if cells is None else (-(-tw >> cells[0]), -(-th >> cells[1]))      # lists per camera: tiles, or cells
+    T = lw * lh * n_cameras
+    # with cells: (cell pairs, tile pairs), written by one launch and copied to the host together
+    n_dev = torch.empty(1 if cells is None else 2, dtype=torch.int64, device=dev)
     n_host = BUFFERS.pinned_i64(dev)
     key = (dev, N, width, height)
     skey = _Buffers._key(dev) + key      # the "static" policy's records are per (device, stream) and frame size
+    bc = None
+    if cells is not None:
+        bc = _lib.BinCells()
+        bc.shift_x, bc.shift_y, bc.n_tile_pairs = cells[0], cells[1], _ptr(n_dev[1:])
 
     prepared_ws = None      # the workspace dnsplat_bin_prepare last ran on in this call
 
@@ -959,62 +1026,120 @@ def bin_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tiles: Tensor, wid
         # the fused path keeps its lists to itself: [start, end) per tile instead of gsplat's offsets (no fill launch)
         a.tile_ends, a.skip_offsets_fill = _ptr(tile_ends), int(tile_ends is not None)
         a.tile_boxes = _ptr(tile_boxes)          # the boxes ``tiles`` were counted over, from the same projection
-        a.n_isects_max = _ptr(BUFFERS.n_max.get(skey))
+        if exact is None:       # the running maxima of the "static" policy: of the list pairs and, with cells, of the tile pairs beside them
+            a.n_isects_max = _ptr(BUFFERS.n_max.get(skey) if cells is None else BUFFERS.n_max_cells.get(skey + cells))
+            if bc is not None:
+                bc.n_tile_pairs_max = _ptr(BUFFERS.n_max.get(skey))
         # the N-sized front of the workspace has the same layout for every capacity, so a depth sort done earlier in this call
         # stays valid for a later emit as long as the buffer was not re-allocated
         if prepared_ws is None or prepared_ws.data_ptr() != ws.data_ptr():
-            _lib.run("dnsplat_bin_prepare", lib.dnsplat_bin_prepare, ctypes.byref(a), _stream())
+            # (the timers know the entry points by their names without the suffix)
+            if bc is None:
+                _lib.run("dnsplat_bin_prepare", lib.dnsplat_bin_prepare, ctypes.byref(a), _stream())
+            else:
+                _lib.run("dnsplat_bin_prepare", lib.dnsplat_bin_prepare_cells, ctypes.byref(a), ctypes.byref(bc), _stream())
             prepared_ws = ws
         return a
 
-    def enqueue(capacity, n_isects, host_slot=n_host, event=None, pending=None) -> Binning:
+    def enqueue(capacity, n_isects, host_slot=n_host, event=None, pending=None, n_tile=None) -> Binning:
         """Depth sort (unless this call has done it), ``event`` recorded behind it (the count is on its way to ``host_slot`` then),
         emit + tile sort into fresh lists of ``capacity`` entries, ``after_emit``."""
         flatten_ids = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
         args = prepare(capacity, flatten_ids, host_slot)
         if event is not None:
             event.record()
-        _lib.run("dnsplat_bin_emit_sort", lib.dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
+        if bc is None:
+            _lib.run("dnsplat_bin_emit_sort", lib.dnsplat_bin_emit_sort, ctypes.byref(args), _stream())
+        else:
+            _lib.run("dnsplat_bin_emit_sort", lib.dnsplat_bin_emit_sort_cells, ctypes.byref(args), ctypes.byref(bc), _stream())
         if pending is not None:
             pending.ring["pending"].append(pending)
-        b = Binning(flatten_ids, tile_offsets, n_isects, tw, th, n_cameras, pending=pending, tile_ends=tile_ends, n_dev=n_dev)
+        b = Binning(flatten_ids, tile_offsets, n_isects, tw, th, n_cameras, pending=pending, tile_ends=tile_ends, n_dev=n_dev[:1])
+        if cells is not None:
+            b.cells, b.list_width, b.list_height = cells, lw, lh
+            b._n_tile, b._n_tile_dev = n_tile, n_dev[1:]
+            b.tile_boxes = tile_boxes       # the compositing kernels read them beside the lists (dnsplat_raster_cells)
         if after_emit is not None:
             after_emit(b)
         return b
+
+    def counts():
+        """(list pairs, tile pairs) of the frame from the host words the depth sort's copy filled."""
+        n = int(n_host[0])
+        return n, (int(n_host[1]) if cells is not None else n)
 
     tile_offsets = torch.empty(T + 1, dtype=torch.int32, device=dev)
     tile_ends = torch.empty(T, dtype=torch.int32, device=dev) if want_ends else None
     mode = BIN_POLICY["mode"]
     if mode in ("deferred", "static") and not defer_ok:
         mode = "capacity"      # callers that hand n_isects / flatten_ids[:n] straight back (the drop-in calls) gain nothing from deferring
-    hint = BUFFERS.capacity_hint.get(key, 0)
+    if exact is not None:
+        return enqueue(exact, exact, host_slot=None)
+    hint = _capacity_guess(key, cells)
     if mode == "static" and hint:
         # nothing on the host depends on the count (a frame captured into a HIP graph): the capacity is the hint, and the
         # device keeps a running maximum of n_isects that static_overflow() compares with it whenever the caller likes
         if skey not in BUFFERS.n_max:
             BUFFERS.n_max[skey] = torch.zeros(1, dtype=torch.int64, device=dev)
-        BUFFERS.static_cap[skey] = min(BUFFERS.static_cap.get(skey, hint), hint)      # the smallest buffers any such frame got
+        tile_hint = BUFFERS.capacity_hint[key]
+        BUFFERS.static_cap[skey] = min(BUFFERS.static_cap.get(skey, tile_hint), tile_hint)      # the smallest buffers any such frame got
+        if cells is not None:
+            if skey + cells not in BUFFERS.n_max_cells:
+                BUFFERS.n_max_cells[skey + cells] = torch.zeros(1, dtype=torch.int64, device=dev)
+            BUFFERS.static_cap_cells[skey + cells] = min(BUFFERS.static_cap_cells.get(skey + cells, hint), hint)
         return enqueue(hint, None, host_slot=None)
     if mode == "deferred" and hint:
         verify_pending_counts(dev)                     # earlier frames whose count has arrived meanwhile (no wait)
         ring, slot, ev = BUFFERS.ring_slot(dev)
-        return enqueue(hint, None, host_slot=slot, event=ev, pending=_PendingCount(ring, slot, ev, hint, key))
+        return enqueue(hint, None, host_slot=slot, event=ev, pending=_PendingCount(ring, slot, ev, hint, key, cells))
     if mode == "capacity" and hint:
         ev = torch.cuda.Event()
         b = enqueue(hint, -1, event=ev)
         ev.synchronize()  # waits for the (early) depth sort only; compositing keeps running
-        n = int(n_host.item())
+        n, n_tile = counts()
         if n <= hint:
             b.n_isects = n
-            BUFFERS.capacity_hint[key] = max(hint, int(n * 1.25) + 4096)
+            b._n_tile = n_tile
+            _learn_capacity(key, cells, n, n_tile)
             return b
         # guess too small: fall through and redo with the exact size
     else:
         prepare(hint, None, n_host)      # the depth sort alone: the host reads the count before anything is emitted
         torch.cuda.current_stream().synchronize()
-        n = int(n_host.item())
-    BUFFERS.capacity_hint[key] = max(hint, int(n * 1.25) + 4096)
-    return enqueue(n, n)
+        n, n_tile = counts()
+    _learn_capacity(key, cells, n, n_tile)
+    return enqueue(n, n, n_tile=n_tile)
+
+
+class _PerTileLists:
+    """The per-tile face of a frame binned over list cells: what a ``Binning`` of the same frame without cells would show.  The count
+    arrives with the cell count (no sort needed); the lists are sorted when somebody reads them — ``build(n)``: the per-tile tile
+    sort of the frame's depths and boxes into lists of exactly n entries, buffers of its own."""
+
+    def __init__(self, cell_binning: Binning, build):
+        self._cells, self._build, self._lists = cell_binning, build, None
+        self.tile_width, self.tile_height, self.n_cameras = cell_binning.tile_width, cell_binning.tile_height, cell_binning.n_cameras
+        self.cells, self.tile_ends = None, None
+
+    pending = property(lambda self: self._cells.pending)
+    _n = property(lambda self: self._cells._n_tile)
+    _n_dev = property(lambda self: self._cells._n_tile_dev)
+    n_isects = property(lambda self: self._cells.n_tile_pairs)
+    n_tile_pairs = n_isects
+
+    def _sorted(self) -> Binning:
+        if self._lists is None:
+            self._lists = self._build(self.n_isects)
+        return self._lists
+
+    flatten_ids = property(lambda self: self._sorted().flatten_ids)
+    tile_offsets = property(lambda self: self._sorted().tile_offsets)
+
+    def filled_offsets(self) -> Tensor:
+        return self._sorted().filled_offsets()
+
+    def verify_if_ready(self) -> None:
+        self._cells.verify_if_ready()
 
 
 class LazyInfo(dict):
@@ -1107,12 +1232,38 @@ def set_deterministic(on: bool) -> None:
     DETERMINISTIC["on"] = bool(on)
 
 
+def _planes(b: "Binning") -> int:
+    """Half tiles that share one list of ``b``: the planes of the keep masks and of the deterministic mode's slot buffer."""
+    return 2 if b.cells is None else 2 << (b.cells[0] + b.cells[1])
+
+
+def _raster_cells(b: "Binning"):
+    """dnsplat_raster_cells for the lists of ``b`` (None: one list per tile)."""
+    if b.cells is None:
+        return None
+    c = _lib.RasterCells()
+    c.shift_x, c.shift_y = b.cells
+    c.tile_boxes = _ptr(b.tile_boxes)       # a tile takes the entries of its cell's list whose own box holds the tile
+    return c
+
+
+def _run_raster(name: str, a: "RasterArgs", b: "Binning") -> None:
+    """``name`` over the lists of ``b``: the entry point itself, or its ``_cells`` form where the lists are per cell (the timers and
+    traces know both by the name without the suffix)."""
+    cells = _raster_cells(b)
+    if cells is None:
+        _lib.run(name, getattr(_lib.lib(), name), ctypes.byref(a), _stream())
+    else:
+        _lib.run(name, getattr(_lib.lib(), name + "_cells"), ctypes.byref(a), ctypes.byref(cells), _stream())
+
+
 def _det_begin(a: "RasterArgs", b: "Binning", dev):
     """Deterministic mode: the zero-filled slot buffer for this launch (None when the mode is off)."""
     if not DETERMINISTIC["on"]:
         return None
     cap = max(int(b.flatten_ids.numel()), 1)
-    part = torch.zeros(2, cap, RECORD_FLOATS, dtype=torch.float32, device=dev)
+    # one plane per half tile that reads a list: its two halves, or every half tile of a list cell
+    part = torch.zeros(_planes(b), cap, RECORD_FLOATS, dtype=torch.float32, device=dev)
     a.det_partials, a.det_capacity = _ptr(part), cap
     return part
 
@@ -1128,7 +1279,10 @@ def _det_finish(part: Optional[Tensor], b: "Binning", v_splats: Tensor) -> None:
     d.n_records, d.capacity = v_splats.shape[0], cap
     d.n_isects, d.flatten_ids, d.partials, d.v_splats = _ptr(n_dev), _ptr(b.flatten_ids), _ptr(part), _ptr(v_splats)
     d.workspace, d.workspace_bytes = _ptr(ws), ws.numel()
-    _lib.run("dnsplat_det_reduce", _lib.lib().dnsplat_det_reduce, ctypes.byref(d), _stream())
+    if part.shape[0] == 2:
+        _lib.run("dnsplat_det_reduce", _lib.lib().dnsplat_det_reduce, ctypes.byref(d), _stream())
+    else:
+        _lib.run("dnsplat_det_reduce", _lib.lib().dnsplat_det_reduce_planes, ctypes.byref(d), part.shape[0], _stream())
 
 
 def _hand_over_means2d_grad(means2d: Tensor, v_splats: Tensor):
@@ -1170,9 +1324,19 @@ def _bin_for(holder, composite, means2d, splats, depths, radii, tiles, width, he
     # stage 2 for a compositing node: ``composite(binning)`` is queued right behind the sort (bin_tiles' ``after_emit``).  The fused
     # path keeps its lists to itself: [start, end) per tile, and a count the host need not wait for
     tight = bool(holder is not None and holder.get("tight"))      # ``tiles`` were counted over the tight boxes
-    b = bin_tiles(means2d.detach().reshape(-1, 2), radii.reshape(-1), depths.detach().reshape(-1), tiles.reshape(-1), width,
-                  height, tile_size, after_emit=composite, n_cameras=C, tight_splats=splats.detach() if tight else None,
-                  defer_ok=fused, want_ends=fused, tile_boxes=holder.get("tile_boxes") if holder is not None else None)
+    tile_boxes = holder.get("tile_boxes") if holder is not None else None
+    # the fused path over tight boxes keeps one list per cell of several tiles (BIN_CELL)
+    cells = _cell_shifts(width, height, tile_size) if (fused and tight and tile_boxes is not None) else None
+    cells = None if cells == (0, 0) else cells
+    m2, rad, dep, til = means2d.detach().reshape(-1, 2), radii.reshape(-1), depths.detach().reshape(-1), tiles.reshape(-1)
+    b = bin_tiles(m2, rad, dep, til, width, height, tile_size, after_emit=composite, n_cameras=C,
+                  tight_splats=splats.detach() if tight else None, defer_ok=fused, want_ends=fused, tile_boxes=tile_boxes, cells=cells)
+    if cells is not None:
+        # what ``info`` shows of such a frame stays per tile: the count is on its way with the cell count, the lists are sorted on
+        # request — the existing per-tile tile sort over the same depths and boxes, into buffers of its own (the cell lists are the
+        # backward's)
+        holder["tile_lists"] = _PerTileLists(b, lambda n: bin_tiles(m2, rad, dep, til, width, height, tile_size, n_cameras=C,
+                                                                    tile_boxes=tile_boxes, exact=n))
     if holder is not None:
         holder["binning"] = b
     return b
@@ -1191,7 +1355,7 @@ def _tile_boxes_into(holder, tight, tile_boxes):
 def _composite_bwd(a: RasterArgs, b: Binning, means2d: Tensor, v_splats: Tensor, absgrad: bool, det: bool = True):
     """Launches the compositing backward over ``a``; returns the gradient to hand to autograd for ``means2d``."""
     part = _det_begin(a, b, v_splats.device) if det else None
-    _lib.run("dnsplat_raster_bwd", _lib.lib().dnsplat_raster_bwd, ctypes.byref(a), _stream())
+    _run_raster("dnsplat_raster_bwd", a, b)
     _det_finish(part, b, v_splats)
     if absgrad:
         # gsplat contract (dn_model.py:512, consumed by nerfstudio after_train via self.xys.absgrad)
@@ -1265,6 +1429,34 @@ KEEP_MASKS = os.environ.get("DNSPLAT_KEEP_MASKS", "1") != "0"
 # ~1/3 fewer intersections on the benchmark scenes, same images and gradients).  DNSPLAT_TIGHT_TILES=0 (or setting this to
 # False) makes it use gsplat's boxes, as the drop-in calls always do.
 TIGHT_TILES = os.environ.get("DNSPLAT_TIGHT_TILES", "1") != "0"
+# With tight tiles the fused path keeps ONE LIST PER CELL of several tiles (dnsplat_bin_cells): its compositing
+# kernels re-test every list entry against their own half tile anyway, and the tile sort then handles a Gaussian once per cell.
+# DNSPLAT_BIN_CELL=WxH (tiles; one of BIN_CELL_SHAPES) or set_bin_cell() picks the cell; 1x1 is one list per tile, the path without cells.
+BIN_CELL_SHAPES = {"1x1": (0, 0), "2x1": (1, 0), "1x2": (0, 1), "2x2": (1, 1), "4x2": (2, 1)}
+# Left to itself the path takes 2x2 cells from BIN_CELL_MIN_TILES tiles per image on: cells shorten the I-sized kernels of the tile sort,
+# and a frame of a few hundred tiles has next to nothing of them — its binning is the fixed cost of its launches, while the compositing
+# kernels would still stage the longer lists (C1, 256 tiles: profiles/ab_cell_lists.txt).  A shape that was ASKED for holds at every size.
+BIN_CELL_MIN_TILES = 1024
+BIN_CELL = {"shifts": (1, 1), "forced": False}
+
+
+def set_bin_cell(shape: Optional[str]) -> None:
+    """``shape``: one of BIN_CELL_SHAPES, at every frame size; None: 2x2 where it pays (BIN_CELL_MIN_TILES)."""
+    if shape is None:
+        BIN_CELL.update(shifts=(1, 1), forced=False)
+        return
+    if shape not in BIN_CELL_SHAPES:
+        raise ValueError(f"DNSPLAT_BIN_CELL: {shape!r} is not one of {sorted(BIN_CELL_SHAPES)}")
+    BIN_CELL.update(shifts=BIN_CELL_SHAPES[shape], forced=True)
+
+
+def _cell_shifts(width: int, height: int, tile_size: int) -> Tuple[int, int]:
+    if not BIN_CELL["forced"] and math.ceil(width / tile_size) * math.ceil(height / tile_size) < BIN_CELL_MIN_TILES:
+        return (0, 0)
+    return BIN_CELL["shifts"]
+
+
+set_bin_cell(os.environ.get("DNSPLAT_BIN_CELL"))
 # dnsplat_raster_args.saturation_flag for the fused path's backward (DNSPLAT_SATURATION_FLAG=0: always the clamping loop)
 SATURATION_FLAG = os.environ.get("DNSPLAT_SATURATION_FLAG", "1") != "0"
 # dnsplat_raster_args.zero_fill: the fused forward clears the gradient records its backward accumulates into
@@ -1342,13 +1534,14 @@ class _RasterDnFn(torch.autograd.Function):
             if KEEP_MASKS:
                 # the forward's rectangle-test ballots, one 64-bit word per (half tile, 64 list entries): the backward takes
                 # them instead of re-testing (and re-gathering) every list entry
-                stride = (b.flatten_ids.numel() >> 6) + C * b.tile_width * b.tile_height + 1
-                keep["masks"], keep["stride"] = torch.empty(2 * stride, dtype=torch.int64, device=dev), stride
+                stride = (b.flatten_ids.numel() >> 6) + C * b.list_width * b.list_height + 1
+                keep["masks"], keep["stride"] = torch.empty(_planes(b) * stride, dtype=torch.int64, device=dev), stride
                 a.keep_masks, a.keep_mask_stride = _ptr(keep["masks"]), stride
+                b.keep = keep          # (for whoever inspects the lists: which of their entries each half tile kept)
             a.dn, a.pair_counters = ctypes.pointer(dn), _ptr(counters)
             if fill["v_splats"] is not None:      # the backward's accumulation buffer, cleared by this launch on the way
                 a.zero_fill, a.zero_fill_bytes = _ptr(fill["v_splats"]), fill["v_splats"].numel() * 4
-            _lib.run("dnsplat_raster_fwd", _lib.lib().dnsplat_raster_fwd, ctypes.byref(a), _stream())
+            _run_raster("dnsplat_raster_fwd", a, b)
 
         b = _bin_for(holder, composite, means2d, splats, depths, radii, tiles, width, height, 16, C, fused=True)
         for c in range(C):

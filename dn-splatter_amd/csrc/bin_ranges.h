@@ -19,6 +19,25 @@
 #define DNS_BR_HD inline
 #endif
 
+// List cells.  The fused path keeps one sorted list per CELL of 2^sx x 2^sy tiles instead of one per tile (its compositing kernels
+// re-test every list entry against their own half tile anyway), so a Gaussian is listed once per cell its tile box touches.
+// The tile box [x0, x0 + w) x [y0, y0 + h) that starts at tile id `base_tile` = y0 * tw + x0 of a grid of `tw` tile columns becomes
+// the cell box [x0 >> sx, ((x0 + w - 1) >> sx) + 1) x [y0 >> sy, ((y0 + h - 1) >> sy) + 1) of the grid of dns_cells(tw, sx) cell
+// columns; an empty box (w == 0 or h == 0: a culled Gaussian) stays empty.  sx == sy == 0 returns the box as it is.
+DNS_BR_HD uint32_t dns_cells(uint32_t tiles, int shift) { return (tiles + (1u << shift) - 1u) >> shift; }
+struct DnsCellBox { uint32_t base, w, h; };        // id of the first cell (row-major over the cell grid), width and height in cells
+DNS_BR_HD DnsCellBox dns_cell_box(uint32_t base_tile, uint32_t w, uint32_t h, uint32_t tw, int sx, int sy)
+{
+    DnsCellBox c;
+    if (w == 0u || h == 0u) { c.base = 0u; c.w = 0u; c.h = 0u; return c; }
+    const uint32_t y0 = base_tile / tw, x0 = base_tile - y0 * tw;
+    const uint32_t cx0 = x0 >> sx, cy0 = y0 >> sy;
+    c.base = cy0 * dns_cells(tw, sx) + cx0;
+    c.w = ((x0 + w - 1u) >> sx) + 1u - cx0;
+    c.h = ((y0 + h - 1u) >> sy) + 1u - cy0;
+    return c;
+}
+
 // Pairs [lo, hi) (0 <= lo < hi <= rows * w) of a record whose box starts at tile id `base`, is `w` tiles wide and lies in a grid of
 // `tw` tile columns.  Calls  range(d0, len)  for every cyclic digit range [d0, d0 + len) (0 < len < 2^dbits, d0 < 2^dbits; the
 // range may wrap past 2^dbits - 1) that receives +1, and returns the constant every digit receives on top.

@@ -20,6 +20,10 @@
 // order the reference's stable 64-bit sort yields, so flatten_ids / tile offsets are bit-identical
 // while the I-sized traffic drops from 6 passes x 12 B to one 6-byte store, one 6-byte load and a 4-byte store.
 //
+// List cells (dnsplat_bin_cells): for a consumer that re-tests every list entry against its own part of a tile anyway, the lists are
+// kept per cell of 2^sx x 2^sy tiles — the boxes are coarsened where they are counted and emitted (dns_cell_box), everything behind
+// sees a grid of cells, and the per-tile pair count is a second sum of the scan.
+//
 // All ranking inside a radix pass is done with wave64 ballots (match-by-digit) and LDS counters:
 // no atomics on the data path (the tile offsets are an atomicMin per (chunk, tile) run), fully
 // deterministic.  Every kernel takes its element count from a
@@ -63,6 +67,22 @@ constexpr int SC_ITEMS = 8;
 constexpr int SC_CHUNK = SC_THREADS * SC_ITEMS;
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (DNS_WAVE - 1); }
+
+// List cells (bin_ranges.h, dnsplat_bin_cells): the lists are kept per cell of 2^sx x 2^sy tiles.  tw = tile columns of one camera's
+// grid, which the projection's tile boxes are numbered over.  sx == sy == 0: one list per tile, nothing below takes another path.
+struct CellGrid {
+    int tw, sx, sy;
+};
+// lists a depth-ordered tile box (first tile id, width | height << 16) enters: its tiles, or the cells they lie in
+__device__ __forceinline__ uint32_t box_lists(int2 b, const CellGrid &cg)
+{
+    const uint32_t w = (uint32_t)b.y & 0xffffu, h = (uint32_t)b.y >> 16;
+    if (cg.sx | cg.sy) {
+        const DnsCellBox c = dns_cell_box((uint32_t)b.x, w, h, (uint32_t)cg.tw, cg.sx, cg.sy);
+        return c.w * c.h;
+    }
+    return w * h;
+}
 
 // ------------------------------------------------------------------------------------------------
 // wave / block scan helpers (wave64 DPP-free version via __shfl_up; these kernels are tiny)
@@ -422,7 +442,7 @@ __global__ __launch_bounds__(TH) DNS_TI_OCCUPANCY(TH, K) void radix_scatter_kern
     const int32_t *__restrict__ radii = nullptr, const float *__restrict__ depths = nullptr,
     int32_t *__restrict__ tile_end = nullptr, GenArgs gen = GenArgs{}, uint32_t *__restrict__ count_out = nullptr,
     const int2 *__restrict__ box_in = nullptr, int2 *__restrict__ box_out = nullptr, uint32_t *__restrict__ tiles_out = nullptr,
-    int segs = 1, int seg_len = 0x7fffffff)
+    int segs = 1, int seg_len = 0x7fffffff, CellGrid cells = CellGrid{})
 {
     // The chunk is first sorted by digit INSIDE LDS (stable), then written out run by run: consecutive lanes
     // store to consecutive addresses of one digit's run, so the stores coalesce.  A direct scatter from the
@@ -589,7 +609,7 @@ __global__ __launch_bounds__(TH) DNS_TI_OCCUPANCY(TH, K) void radix_scatter_kern
             if ((uint32_t)(r * TH + threadIdx.x) < n_out) {
                 vals_out[dsts[r]] = vs[r];
                 box_out[dsts[r]] = bx[r];
-                tiles_out[dsts[r]] = ((uint32_t)bx[r].y & 0xffffu) * ((uint32_t)bx[r].y >> 16);
+                tiles_out[dsts[r]] = box_lists(bx[r], cells);
             }
         return;
     }
@@ -893,7 +913,7 @@ __device__ __forceinline__ void dp_lsd_pass(const uint2 *src, uint2 *dst, uint32
 // together (one by one, each round of the loop was a gather's latency).
 __device__ __forceinline__ void dp_store_bucket(const uint2 *res, uint32_t s, uint32_t n, uint32_t *__restrict__ vals_out,
                                                 const int2 *__restrict__ box_in, int2 *__restrict__ box_out,
-                                                uint32_t *__restrict__ tiles_out)
+                                                uint32_t *__restrict__ tiles_out, const CellGrid &cells)
 {
     constexpr int U = 4;
     for (uint32_t i0 = threadIdx.x; i0 < n; i0 += U * DP_THREADS) {
@@ -912,7 +932,7 @@ __device__ __forceinline__ void dp_store_bucket(const uint2 *res, uint32_t s, ui
                 vals_out[s + i] = v[u];
                 if (box_in) {
                     box_out[s + i] = bx[u];
-                    tiles_out[s + i] = ((uint32_t)bx[u].y & 0xffffu) * ((uint32_t)bx[u].y >> 16);
+                    tiles_out[s + i] = box_lists(bx[u], cells);
                 }
             }
         }
@@ -1001,7 +1021,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_bucket_sort_kernel(const uin
                                                                        const uint32_t *__restrict__ bucket_start, uint2 *pairs_a,
                                                                        uint2 *pairs_b, uint32_t *__restrict__ vals_out,
                                                                        const int2 *__restrict__ box_in, int2 *__restrict__ box_out,
-                                                                       uint32_t *__restrict__ tiles_out)
+                                                                       uint32_t *__restrict__ tiles_out, CellGrid cells)
 {
     __shared__ uint2 buf[DP_CAP];
     __shared__ uint32_t dig_run[256];
@@ -1014,14 +1034,14 @@ __global__ __launch_bounds__(DP_THREADS) void depth_bucket_sort_kernel(const uin
     const int passes = dns_depth_local_passes(shift), dbits = dns_depth_local_bits(shift);
     if (n <= (uint32_t)DP_CAP) {
         dp_sort_in_lds(pairs_a + s, n, kmin, passes, dbits, buf, dig_run, wave_cnt, lds_wave);
-        dp_store_bucket(buf, s, n, vals_out, box_in, box_out, tiles_out);
+        dp_store_bucket(buf, s, n, vals_out, box_in, box_out, tiles_out, cells);
     } else {
         uint2 *src = pairs_a + s, *dst = pairs_b + s;
         for (int p = 0; p < passes; ++p) {
             dp_lsd_pass(src, dst, n, kmin, p * dbits, dbits, dig_run, wave_cnt, lds_wave);
             uint2 *t = src; src = dst; dst = t;
         }
-        dp_store_bucket(src, s, n, vals_out, box_in, box_out, tiles_out);
+        dp_store_bucket(src, s, n, vals_out, box_in, box_out, tiles_out, cells);
     }
 }
 
@@ -1077,8 +1097,12 @@ __global__ __launch_bounds__(SC_THREADS) void scan_sums_kernel(int N, const uint
 }
 
 // scan_sums_kernel when the last depth pass has already left the counts in depth order (radix_scatter_kernel<..., BOXG>): a coalesced sum
+// tile_sums (with boxes_sorted; or NULL): a second sum of the same walk, the TILES of the boxes — what the lists would hold if they were kept
+// per tile.  With list cells the counts in tiles_sorted are cells; the per-tile pair count stays known without a per-tile sort.
 __global__ __launch_bounds__(SC_THREADS) void scan_sums_sorted_kernel(int N, const uint32_t *__restrict__ n_ptr,
-                                                                      const uint32_t *__restrict__ tiles_sorted, uint32_t *__restrict__ sums)
+                                                                      const uint32_t *__restrict__ tiles_sorted, uint32_t *__restrict__ sums,
+                                                                      const int2 *__restrict__ boxes_sorted = nullptr,
+                                                                      uint32_t *__restrict__ tile_sums = nullptr)
 {
     __shared__ uint32_t lds_wave[4];
     const int n = (int)min(*n_ptr, (uint32_t)N);
@@ -1090,6 +1114,17 @@ __global__ __launch_bounds__(SC_THREADS) void scan_sums_sorted_kernel(int N, con
     uint32_t tot;
     block_incl_scan_256(s, lds_wave, tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+    if (tile_sums) {
+        uint32_t f = 0;
+#pragma unroll
+        for (int i = 0; i < SC_ITEMS; ++i)
+            if (base + i < n) {
+                const uint32_t wh = (uint32_t)boxes_sorted[base + i].y;
+                f += (wh & 0xffffu) * (wh >> 16);
+            }
+        block_incl_scan_256(f, lds_wave, tot);
+        if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
+    }
 }
 
 // What the pair generators of the tile sort's first pass need per Gaussian (EmitRec, by depth rank) and per 4096-pair chunk
@@ -1104,6 +1139,7 @@ struct EmitPrep {
     const float4 *__restrict__ splats;   // tight tile boxes (dnsplat_bin_args.tight_tiles): the box the projection kernel counted
     const int2 *__restrict__ boxes;      // or NULL: (first tile id within the camera's grid, width | height << 16) straight from the projection
     const int2 *__restrict__ boxes_sorted;   // the same records in depth order (the depth sort left them): read by rank, no gather
+    CellGrid cells;                      // list cells (needs boxes): tw / th above are then the CELL grid, cells.tw the tile columns the boxes count in
 };
 
 // depth rank j = entry gid owns the pairs [start, end) of the emission order, end > start
@@ -1119,6 +1155,11 @@ __device__ __forceinline__ void emit_record(const EmitPrep &ep, int N, uint32_t 
         const int2 b = ep.boxes_sorted ? ep.boxes_sorted[j] : ep.boxes[gid];
         r.bw = (uint32_t)b.y & 0xffffu;
         r.base_tile = (uint32_t)b.x + cam_tiles;
+        if (ep.cells.sx | ep.cells.sy) {
+            const DnsCellBox c = dns_cell_box((uint32_t)b.x, r.bw, (uint32_t)b.y >> 16, (uint32_t)ep.cells.tw, ep.cells.sx, ep.cells.sy);
+            r.bw = c.w;
+            r.base_tile = c.base + cam_tiles;
+        }
     } else {
         int x0, y0, x1, y1;
         if (ep.splats) {
@@ -1139,12 +1180,30 @@ __global__ __launch_bounds__(SC_THREADS) void scan_final_kernel(int N, const uin
                                                                 const int32_t *__restrict__ tiles,
                                                                 const uint32_t *__restrict__ sums,
                                                                 uint32_t *__restrict__ cum, uint32_t *__restrict__ total_u32,
-                                                                int64_t *__restrict__ total_i64, int64_t *__restrict__ total_max)
+                                                                int64_t *__restrict__ total_i64, int64_t *__restrict__ total_max,
+                                                                const uint32_t *__restrict__ tile_sums = nullptr,
+                                                                int64_t *__restrict__ tile_pairs = nullptr,
+                                                                int64_t *__restrict__ tile_pairs_max = nullptr)
 {
     __shared__ uint32_t lds_wave[4];
     const int n = (int)min(*n_ptr, (uint32_t)N);
-    if (n == 0 && blockIdx.x == 0 && threadIdx.x == 0) { *total_u32 = 0u; *total_i64 = 0; }
+    if (n == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+        *total_u32 = 0u; *total_i64 = 0;
+        if (tile_pairs) *tile_pairs = 0;
+    }
     if (blockIdx.x * SC_CHUNK >= n) return;
+    // the workgroup of the last depth rank also adds up the per-tile counts of all chunks (scan_sums_sorted_kernel): the second total
+    // and its sticky maximum
+    if (tile_pairs && (n - 1) / SC_CHUNK == (int)blockIdx.x) {
+        uint32_t f = 0;
+        for (int c = threadIdx.x; c <= (int)blockIdx.x; c += SC_THREADS) f += tile_sums[c];
+        uint32_t ftot;
+        block_incl_scan_256(f, lds_wave, ftot);
+        if (threadIdx.x == 0) {
+            *tile_pairs = (int64_t)ftot;
+            if (tile_pairs_max) atomicMax(reinterpret_cast<unsigned long long *>(tile_pairs_max), (unsigned long long)ftot);
+        }
+    }
     const int base = blockIdx.x * SC_CHUNK + threadIdx.x * SC_ITEMS;
     uint32_t v[SC_ITEMS];
     uint32_t s = 0;
@@ -1256,6 +1315,7 @@ struct BinWs {
     uint32_t *tab_n;                          // [256 * nb_n]
     uint32_t *totals;                         // [256 x SC_MAX_SEGS] segment sums of the digit scans
     uint32_t *sums;                           // [nb_scan]
+    uint32_t *tile_sums;                      // [nb_scan] per-tile counts of the same chunks (dnsplat_bin_cells.n_tile_pairs)
     uint32_t *total;                          // [1] n_isects as u32
     uint32_t *status;                         // [1] reserved status word (dnsplat_bin_status_offset): 0
     uint32_t *n_ranked;                       // [1] Gaussians the depth sort kept (radii > 0) = number of depth ranks
@@ -1304,6 +1364,9 @@ BinWs carve(void *ws, int N, int64_t cap)
     b.tab_n = take((size_t)RS_DIGITS * b.nb_n);
     b.totals = take((size_t)RS_DIGITS * SC_MAX_SEGS);
     b.sums = take(b.nb_scan);
+    // no room of its own (the workspace is the parent's, byte for byte): written and read behind the depth sort, whose second key buffer
+    // (the four-pass route's; part of the partition's count table) is dead by then.  nb_scan <= max(N, 1) words
+    b.tile_sums = b.key_b;
     b.total = take(1);
     b.status = take(1);
     b.n_ranked = take(1);
@@ -1369,6 +1432,7 @@ struct BoxGather {
     const int2 *boxes;
     int2 *boxes_sorted;
     uint32_t *tiles_sorted;
+    CellGrid cells;              // tiles_sorted counts the cells of a box instead of its tiles
 };
 
 // A plain 8-bit pass over 32-bit keys: passes 1-3 of the four-pass depth sort and every pass of dnsplat_det_reduce.  gather: the box
@@ -1383,7 +1447,7 @@ void depth_pass(hipStream_t stream, const uint32_t *ka, const uint32_t *va, uint
     if (gather)
         hipLaunchKernelGGL((radix_scatter_kernel<uint32_t, false, 8, ITEMS, false, false, RS_THREADS, true>), dim3(t.nb), dim3(RS_THREADS), 0, stream,
                            ka, va, kb, vb, n_ptr, n_cap, shift, t.table, t.totals, t.nb, nullptr, nullptr, nullptr, nullptr, GenArgs{}, nullptr,
-                           gather->boxes, gather->boxes_sorted, gather->tiles_sorted, s.segs, s.seg_len);
+                           gather->boxes, gather->boxes_sorted, gather->tiles_sorted, s.segs, s.seg_len, gather->cells);
     else
         hipLaunchKernelGGL((radix_scatter_kernel<uint32_t, false, 8, ITEMS, false, false, RS_THREADS, false>), dim3(t.nb), dim3(RS_THREADS), 0, stream,
                            ka, va, kb, vb, n_ptr, n_cap, shift, t.table, t.totals, t.nb, nullptr, nullptr, nullptr, nullptr, GenArgs{}, nullptr,
@@ -1480,10 +1544,10 @@ void emit_and_sort(hipStream_t stream, const dnsplat_bin_args *a, const BinWs &w
 // The four-pass depth sort of dnsplat_bin_prepare: leaves the depth order in w.val_a.  boxes != NULL: the last pass leaves the tile boxes
 // and the tile counts in depth order beside it.
 template <int ITEMS>
-void depth_sort_radix4(hipStream_t stream, const dnsplat_bin_args *a, const BinWs &w, const int2 *boxes)
+void depth_sort_radix4(hipStream_t stream, const dnsplat_bin_args *a, const BinWs &w, const int2 *boxes, const CellGrid &cells)
 {
     const DigitTable t{w.tab_n, w.totals, w.nb_n};
-    const BoxGather gather{boxes, w.boxes_sorted, w.tiles_sorted};
+    const BoxGather gather{boxes, w.boxes_sorted, w.tiles_sorted, cells};
     const uint32_t n = (uint32_t)a->N;
     uint32_t *ka = w.key_a, *kb = w.key_b, *va = w.val_a, *vb = w.val_b;
     for (int pass = 0; pass < 4; ++pass) {
@@ -1543,10 +1607,11 @@ __global__ __launch_bounds__(256) void det_iota_kernel(const int64_t *__restrict
 }
 
 // 16 lanes per entry of the record-sorted list (lane & 15 = column of the gradient record); the group whose entry is the first of
-// its record adds up the record's rows: for each of its entries in list order, half 0 then half 1 — a fixed order, in double.
+// its record adds up the record's rows: for each of its entries in list order, half 0 then half 1 (with list cells: the planes of the
+// cell's half tiles in ascending order) — a fixed order, in double.
 __global__ __launch_bounds__(256) void det_reduce_kernel(const uint32_t *__restrict__ count, const uint32_t *__restrict__ keys,
                                                          const uint32_t *__restrict__ vals, const float *__restrict__ partials,
-                                                         size_t cap, int n_records, float *__restrict__ v_splats)
+                                                         size_t cap, int n_records, float *__restrict__ v_splats, int n_planes)
 {
     const uint32_t n = *count;
     const uint32_t i = (uint32_t)(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
@@ -1557,8 +1622,7 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(const uint32_t *__restr
     double acc = 0.0;
     for (uint32_t j = i; j < n && keys[j] == g; ++j) {
         const size_t e = vals[j];
-        acc += (double)partials[e * DNS_REC + col];
-        acc += (double)partials[(cap + e) * DNS_REC + col];
+        for (int p = 0; p < n_planes; ++p) acc += (double)partials[((size_t)p * cap + e) * DNS_REC + col];
     }
     v_splats[(size_t)g * DNS_REC + col] = (float)acc;
 }
@@ -1571,9 +1635,11 @@ extern "C" size_t dnsplat_det_workspace_bytes(int64_t capacity)
     return det_carve(nullptr, capacity).bytes;
 }
 
-extern "C" int dnsplat_det_reduce(const dnsplat_det_args *a, dnsplat_stream_t stream_)
+extern "C" int dnsplat_det_reduce(const dnsplat_det_args *a, dnsplat_stream_t stream) { return dnsplat_det_reduce_planes(a, 2, stream); }
+
+extern "C" int dnsplat_det_reduce_planes(const dnsplat_det_args *a, int32_t n_planes, dnsplat_stream_t stream_)
 {
-    if (!a || a->n_records < 0 || a->capacity < 0 || a->capacity > 0x7fffffffLL) return DNSPLAT_ERR_INVALID_ARG;
+    if (!a || a->n_records < 0 || a->capacity < 0 || a->capacity > 0x7fffffffLL || n_planes < 1) return DNSPLAT_ERR_INVALID_ARG;
     if (a->capacity == 0 || a->n_records == 0) return DNSPLAT_OK;
     if (!a->n_isects || !a->flatten_ids || !a->partials || !a->v_splats || !a->workspace) return DNSPLAT_ERR_INVALID_ARG;
     if (a->workspace_bytes < det_carve(nullptr, a->capacity).bytes) return DNSPLAT_ERR_WORKSPACE;
@@ -1595,7 +1661,7 @@ extern "C" int dnsplat_det_reduce(const dnsplat_det_args *a, dnsplat_stream_t st
     }
     const size_t groups = (size_t)cap;
     hipLaunchKernelGGL(det_reduce_kernel, dim3((unsigned)((groups * 16 + 255) / 256)), dim3(256), 0, stream, w.count, ka, va, a->partials,
-                       (size_t)a->capacity, a->n_records, a->v_splats);
+                       (size_t)a->capacity, a->n_records, a->v_splats, n_planes);
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
 }
@@ -1631,6 +1697,33 @@ static bool depth_sort_by_partition(int N)
 // found by symbol (tests, A/B scripts); not part of include/dnsplat.h.
 extern "C" int dnsplat_bin_depth_route(int32_t N) { return depth_sort_by_partition(N) ? 1 : 0; }
 
+// The list grid of a launch: (tw, th) lists per camera, and for the kernels that read tile boxes the grid those are numbered over.
+struct ListGrid {
+    int tw, th;          // cells per camera (the tiles themselves without dnsplat_bin_cells)
+    CellGrid cells;
+};
+static ListGrid list_grid(const dnsplat_bin_args *a, const dnsplat_bin_cells *c)
+{
+    ListGrid g;
+    const int tw = dns_tiles_w(a->width, a->tile_size), th = dns_tiles_h(a->height, a->tile_size);
+    g.cells = CellGrid{tw, c ? c->shift_x : 0, c ? c->shift_y : 0};
+    g.tw = (int)dns_cells((uint32_t)tw, g.cells.sx);
+    g.th = (int)dns_cells((uint32_t)th, g.cells.sy);
+    return g;
+}
+
+// cells are cut out of the projection's tile boxes, and the per-tile count is the second sum over them
+static int check_cells(const dnsplat_bin_args *a, const dnsplat_bin_cells *c)
+{
+    if (!c) return DNSPLAT_OK;
+    if (c->shift_x < 0 || c->shift_x > 4 || c->shift_y < 0 || c->shift_y > 4) return DNSPLAT_ERR_INVALID_ARG;
+    if (((c->shift_x | c->shift_y) != 0 || c->n_tile_pairs) && a->N > 0 && !a->tile_boxes) return DNSPLAT_ERR_INVALID_ARG;
+    if (c->n_tile_pairs_max && !c->n_tile_pairs) return DNSPLAT_ERR_INVALID_ARG;
+    // one copy brings both counts to the host
+    if (c->n_tile_pairs && a->n_isects_host && c->n_tile_pairs != a->n_isects + 1) return DNSPLAT_ERR_INVALID_ARG;
+    return DNSPLAT_OK;
+}
+
 static int check_bin(const dnsplat_bin_args *a)
 {
     if (!a) return DNSPLAT_ERR_INVALID_ARG;
@@ -1643,17 +1736,23 @@ static int check_bin(const dnsplat_bin_args *a)
     return DNSPLAT_OK;
 }
 
-extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t stream_)
+extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t stream) { return dnsplat_bin_prepare_cells(a, nullptr, stream); }
+
+extern "C" int dnsplat_bin_prepare_cells(const dnsplat_bin_args *a, const dnsplat_bin_cells *cells, dnsplat_stream_t stream_)
 {
     int rc = check_bin(a);
+    if (rc == DNSPLAT_OK) rc = check_cells(a, cells);
     if (rc != DNSPLAT_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_;
+    const ListGrid grid = list_grid(a, cells);
+    int64_t *tile_pairs = cells ? cells->n_tile_pairs : nullptr;
     BinWs w = carve(a->workspace, a->N, a->isect_capacity);
     const int N = a->N;
     if (a->tight_tiles && !a->splats && !a->tile_boxes && N > 0) return DNSPLAT_ERR_INVALID_ARG;
     if (N == 0) {
         if (hipMemsetAsync(a->n_isects, 0, sizeof(int64_t), stream) != hipSuccess) return DNSPLAT_ERR_LAUNCH;
         if (hipMemsetAsync(w.total, 0, sizeof(uint32_t), stream) != hipSuccess) return DNSPLAT_ERR_LAUNCH;
+        if (tile_pairs && hipMemsetAsync(tile_pairs, 0, sizeof(int64_t), stream) != hipSuccess) return DNSPLAT_ERR_LAUNCH;
     } else {
         const uint32_t n_u32 = (uint32_t)N;
         // the projection's tile boxes, or NULL: the depth sort gathers them on the way (its last pass or its bucket sorts) and leaves them
@@ -1683,12 +1782,14 @@ extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t s
             }
 #undef DNS_DEPTH_PARTITION
             hipLaunchKernelGGL(depth_bucket_sort_kernel, dim3(1 << bbits), dim3(DP_THREADS), 0, stream, w.dp_ks, w.dp_start, pairs_a, pairs_b,
-                               w.val_a, boxes, w.boxes_sorted, w.tiles_sorted);
-        } else if (rs_items_n(N) == RS_ITEMS_N_LARGE) depth_sort_radix4<RS_ITEMS_N_LARGE>(stream, a, w, boxes);
-        else depth_sort_radix4<RS_ITEMS_N>(stream, a, w, boxes);
-        // either way the depth order is in val_a now, and with boxes the tile counts in tiles_sorted
+                               w.val_a, boxes, w.boxes_sorted, w.tiles_sorted, grid.cells);
+        } else if (rs_items_n(N) == RS_ITEMS_N_LARGE) depth_sort_radix4<RS_ITEMS_N_LARGE>(stream, a, w, boxes, grid.cells);
+        else depth_sort_radix4<RS_ITEMS_N>(stream, a, w, boxes, grid.cells);
+        // either way the depth order is in val_a now, and with boxes the tile (cell) counts in tiles_sorted and the boxes, still in tiles, in
+        // boxes_sorted
         if (boxes)
-            hipLaunchKernelGGL(scan_sums_sorted_kernel, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.tiles_sorted, w.sums);
+            hipLaunchKernelGGL(scan_sums_sorted_kernel, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.tiles_sorted, w.sums,
+                               tile_pairs ? w.boxes_sorted : nullptr, tile_pairs ? w.tile_sums : nullptr);
         else
             hipLaunchKernelGGL(scan_sums_kernel<false>, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.val_a, a->tiles_per_gauss,
                                w.sums, w.tiles_sorted);
@@ -1696,32 +1797,38 @@ extern "C" int dnsplat_bin_prepare(const dnsplat_bin_args *a, dnsplat_stream_t s
         ep.jrec = w.jrec; ep.chunk_first = w.chunk_first; ep.nb_chunks = MAX_CHUNKS; ep.chunk = RS_THREADS * RS_ITEMS_I;
         ep.n_per_cam = N / (a->n_cameras > 1 ? a->n_cameras : 1);
         ep.tile_size = a->tile_size;
-        ep.tw = dns_tiles_w(a->width, a->tile_size); ep.th = dns_tiles_h(a->height, a->tile_size);
+        ep.tw = grid.tw; ep.th = grid.th;
+        ep.cells = grid.cells;
         ep.means2d = a->means2d; ep.radii = a->radii;
         ep.splats = a->tight_tiles ? reinterpret_cast<const float4 *>(a->splats) : nullptr;
         ep.boxes = boxes;
         ep.boxes_sorted = boxes ? w.boxes_sorted : nullptr;
         hipLaunchKernelGGL(scan_final_kernel, dim3(w.nb_scan), dim3(SC_THREADS), 0, stream, N, w.n_ranked, w.val_a,
-                           (const int32_t *)w.tiles_sorted, w.sums, w.cum, w.total, a->n_isects, a->n_isects_max);
+                           (const int32_t *)w.tiles_sorted, w.sums, w.cum, w.total, a->n_isects, a->n_isects_max, w.tile_sums, tile_pairs,
+                           cells ? cells->n_tile_pairs_max : nullptr);
         hipLaunchKernelGGL(emit_prep_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, w.n_ranked, w.val_a, w.cum, ep);
         DNS_CHECK_LAUNCH();
     }
     if (a->n_isects_host) {
-        if (hipMemcpyAsync(a->n_isects_host, a->n_isects, sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess)
+        if (hipMemcpyAsync(a->n_isects_host, a->n_isects, (tile_pairs ? 2 : 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess)
             return DNSPLAT_ERR_LAUNCH;
     }
     return DNSPLAT_OK;
 }
 
-extern "C" int dnsplat_bin_emit_sort(const dnsplat_bin_args *a, dnsplat_stream_t stream_)
+extern "C" int dnsplat_bin_emit_sort(const dnsplat_bin_args *a, dnsplat_stream_t stream) { return dnsplat_bin_emit_sort_cells(a, nullptr, stream); }
+
+extern "C" int dnsplat_bin_emit_sort_cells(const dnsplat_bin_args *a, const dnsplat_bin_cells *cells, dnsplat_stream_t stream_)
 {
     int rc = check_bin(a);
+    if (rc == DNSPLAT_OK) rc = check_cells(a, cells);
     if (rc != DNSPLAT_OK) return rc;
     if (!a->tile_offsets || (a->isect_capacity > 0 && !a->flatten_ids)) return DNSPLAT_ERR_INVALID_ARG;
     if (a->tight_tiles && !a->splats && !a->tile_boxes && a->N > 0) return DNSPLAT_ERR_INVALID_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     BinWs w = carve(a->workspace, a->N, a->isect_capacity);
-    const int tw = dns_tiles_w(a->width, a->tile_size), th = dns_tiles_h(a->height, a->tile_size);
+    const ListGrid grid = list_grid(a, cells);
+    const int tw = grid.tw, th = grid.th;          // the lists: tiles, or cells
     const int64_t n_tiles64 = (int64_t)tw * th * (a->n_cameras > 1 ? a->n_cameras : 1);
     if (n_tiles64 > 0x7fffffffLL) return DNSPLAT_ERR_UNSUPPORTED;
     const int n_tiles = (int)n_tiles64;

@@ -107,8 +107,9 @@ struct BwdArgs {
     const float *__restrict__ v_alphas;
     int xy_split;
     float *__restrict__ v_splats;
-    // DET instantiations (dnsplat_raster_args.det_partials): the record of (half tile `part`, list entry idx) is STORED at
-    // det + (part * det_cap + idx) * 16 instead of being added atomically to v_splats[gaussian]
+    // DET instantiations (dnsplat_raster_args.det_partials): the record of (half tile of plane p, list entry idx) is STORED at
+    // det + (p * det_cap + idx) * 16 instead of being added atomically to v_splats[gaussian]; p = the half (`part`), with list cells
+    // the half tile's position inside its cell
     float *__restrict__ det;
     long long det_cap;
     // fused dn-splatter epilogue (DN instantiation only): cotangents of rgb / filled depth / normal / accumulation
@@ -117,6 +118,9 @@ struct BwdArgs {
     const float *__restrict__ dn_v_depth;
     const float *__restrict__ dn_v_normal;
     const float *__restrict__ dn_v_acc;
+    // list cells (DN instantiations only, dnsplat_raster_cells; as FwdArgs in raster_fwd.hip): csx == csy == 0 is one list per tile
+    int csx, csy, ctw, n_cells;
+    const int2 *__restrict__ tile_boxes;       // with cells: the entries' own tile boxes (instantiations that cull themselves), else NULL
 };
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -178,7 +182,8 @@ __device__ __forceinline__ f2 pk_mul_bcast(f2 a, f2 b, int hi)
 // halves a Gaussian touches reach its gradient record is not, and fp32 addition does not commute with that.  DET stores every
 // row in its own slot of a buffer indexed by (half, sorted list index) instead; dnsplat_det_reduce adds up each Gaussian's slots in
 // list order.  The last bucket is not folded (a folded splat sits in 2 or 4 lanes, i.e. would have 2 or 4 rows for one slot).
-template <int D, int SPLIT, bool DN, bool COUNT = false, bool MASKS = false, bool CLAMP_LOOP = true, bool DET = false>
+// CELLS: the lists are per cell of several tiles (dnsplat_raster_cells; fused pass only); without it the kernel is the one it was before.
+template <int D, int SPLIT, bool DN, bool COUNT = false, bool MASKS = false, bool CLAMP_LOOP = true, bool DET = false, bool CELLS = false>
 __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT && !DET) void raster_bwd_kernel(BwdArgs a)
 {
     if (a.sat_flag && (*a.sat_flag != 0u) != CLAMP_LOOP) return;
@@ -199,8 +204,16 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
     const size_t img = (size_t)cam * a.width * a.height;
     const int part = blockIdx.x % PARTS;
     const int lane = threadIdx.x;
-    const int range_start = a.tile_offsets[cam * a.n_tiles + tile];
-    const int range_end = a.tile_ends ? a.tile_ends[cam * a.n_tiles + tile] : a.tile_offsets[cam * a.n_tiles + tile + 1];
+    // the list this half tile replays and its plane in the keep masks / the DET buffer: the tile's own list and the half, or (DN) the
+    // list of the tile's cell and the half tile's position inside it (the forward's numbering)
+    int list = cam * a.n_tiles + tile, plane = part;
+    if (CELLS) {
+        const int tx = tile % a.tw, ty = tile / a.tw;
+        list = cam * a.n_cells + (ty >> a.csy) * a.ctw + (tx >> a.csx);
+        plane = ((((ty & ((1 << a.csy) - 1)) << a.csx) | (tx & ((1 << a.csx) - 1))) << 1) | part;
+    }
+    const int range_start = a.tile_offsets[list];
+    const int range_end = a.tile_ends ? a.tile_ends[list] : a.tile_offsets[list + 1];
     if (range_end <= range_start) return;
     [[maybe_unused]] unsigned long long n_slots = 0, n_pairs = 0;
 #ifdef DNS_BWD_TIMELINE
@@ -326,7 +339,9 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
     // MASKS: entries are taken in the forward's batches of 64 (aligned to the start of the list), highest batch first
     [[maybe_unused]] int batch = (hi - range_start) >> 6;
     [[maybe_unused]] const unsigned long long *masks =
-        MASKS ? a.keep_masks + (size_t)part * a.keep_mask_stride + (range_start >> 6) + cam * a.n_tiles + tile : nullptr;
+        !MASKS ? nullptr
+               : CELLS ? a.keep_masks + (size_t)plane * a.keep_mask_stride + (range_start >> 6) + list
+                       : a.keep_masks + (size_t)part * a.keep_mask_stride + (range_start >> 6) + cam * a.n_tiles + tile;
     [[maybe_unused]] const uint64_t gt_mask = (lane == 63) ? 0ull : (~0ull << (lane + 1));
     int qn = 0;       // entries waiting in the queue beyond the current bucket (wave-uniform)
     const uint32_t pix_base = (uint32_t)(uintptr_t)&pix[0][0];   // LDS byte address of the table
@@ -384,6 +399,8 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
                 const int g = a.flatten_ids[idx];
                 const float4 r0 = a.splats[(size_t)g * 4], r1 = a.splats[(size_t)g * 4 + 1];
                 keep = !dns_cull_rect(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, fx0, rxh, fy0, ryh);
+                // list cells: only the entries whose own tile box holds this tile are the tile's (the forward's rule)
+                if (CELLS) keep = keep && dns_tile_in_box(a.tile_boxes[g], tile % a.tw, tile / a.tw, a.tw, 1.f / (float)a.tw);
             }
             const uint64_t m = dns_ballot(keep);
             if (keep) queue[qn + __popcll(m & lt_mask)] = idx;
@@ -431,7 +448,7 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
                         for (int k = 0; k < 8; ++k) row[REC_CH0 + k] = g_ch[k];
                         row[REC_ABSX] = -XY_SCALE * g_ax; row[REC_ABSX + 1] = -XY_SCALE * g_ay;
                         // DET: the row's own slot, keyed by the splat's list index (every (half tile, entry) is flushed exactly once)
-                        float *base = DET ? a.det + (size_t)part * (size_t)a.det_cap * DNS_REC : a.v_splats;
+                        float *base = DET ? a.det + (size_t)plane * (size_t)a.det_cap * DNS_REC : a.v_splats;
                         ulonglong2 ad;
                         ad.x = cmp_a != 0x7fffffff ? (unsigned long long)(uintptr_t)(base + (size_t)(DET ? cmp_a : gid_a) * DNS_REC) : ~0ull;
                         ad.y = cmp_b != 0x7fffffff ? (unsigned long long)(uintptr_t)(base + (size_t)(DET ? cmp_b : gid_b) * DNS_REC) : ~0ull;
@@ -675,18 +692,18 @@ __global__ __launch_bounds__(DNS_WAVE) DNS_BWD_OCCUPANCY(DN && MASKS && !COUNT &
 #endif
 }
 
-template <int D, int SPLIT, bool DN = false, bool COUNT = false, bool MASKS = false>
+template <int D, int SPLIT, bool DN = false, bool COUNT = false, bool MASKS = false, bool CELLS = false>
 int launch_bwd(const BwdArgs &ba, hipStream_t stream)
 {
     if constexpr (!COUNT) if (ba.det) {                  // deterministic scatter: always the clamping loop, never folded
-        hipLaunchKernelGGL((raster_bwd_kernel<D, SPLIT, DN, false, MASKS, true, true>), dim3(ba.n_tiles * ba.n_cameras * PARTS), dim3(DNS_WAVE), 0, stream, ba);
+        hipLaunchKernelGGL((raster_bwd_kernel<D, SPLIT, DN, false, MASKS, true, true, CELLS>), dim3(ba.n_tiles * ba.n_cameras * PARTS), dim3(DNS_WAVE), 0, stream, ba);
         DNS_CHECK_LAUNCH();
         return DNSPLAT_OK;
     }
-    hipLaunchKernelGGL((raster_bwd_kernel<D, SPLIT, DN, COUNT, MASKS, true>), dim3(ba.n_tiles * ba.n_cameras * PARTS), dim3(DNS_WAVE), 0, stream, ba);
+    hipLaunchKernelGGL((raster_bwd_kernel<D, SPLIT, DN, COUNT, MASKS, true, false, CELLS>), dim3(ba.n_tiles * ba.n_cameras * PARTS), dim3(DNS_WAVE), 0, stream, ba);
     DNS_CHECK_LAUNCH();
     if constexpr (DN && !COUNT) if (ba.sat_flag) {       // its clamp-free twin; exactly one of the two does the work
-        hipLaunchKernelGGL((raster_bwd_kernel<D, SPLIT, DN, COUNT, MASKS, false>), dim3(ba.n_tiles * ba.n_cameras * PARTS), dim3(DNS_WAVE), 0, stream, ba);
+        hipLaunchKernelGGL((raster_bwd_kernel<D, SPLIT, DN, COUNT, MASKS, false, false, CELLS>), dim3(ba.n_tiles * ba.n_cameras * PARTS), dim3(DNS_WAVE), 0, stream, ba);
         DNS_CHECK_LAUNCH();
     }
     return DNSPLAT_OK;
@@ -702,9 +719,14 @@ int dispatch_split(const BwdArgs &ba, hipStream_t stream)
 
 }  // namespace
 
-extern "C" int dnsplat_raster_bwd(const dnsplat_raster_args *a, dnsplat_stream_t stream_)
+extern "C" int dnsplat_raster_bwd(const dnsplat_raster_args *a, dnsplat_stream_t stream) { return dnsplat_raster_bwd_cells(a, nullptr, stream); }
+
+extern "C" int dnsplat_raster_bwd_cells(const dnsplat_raster_args *a, const dnsplat_raster_cells *cells, dnsplat_stream_t stream_)
 {
     if (!a) return DNSPLAT_ERR_INVALID_ARG;
+    const int csx = cells ? cells->shift_x : 0, csy = cells ? cells->shift_y : 0;
+    if (csx < 0 || csx > 4 || csy < 0 || csy > 4) return DNSPLAT_ERR_INVALID_ARG;
+    if ((csx | csy) && !a->dn) return DNSPLAT_ERR_UNSUPPORTED;       // only the fused pass reads per-cell lists
     if (a->tile_size != TILE) return DNSPLAT_ERR_UNSUPPORTED;
     if (a->D < 1 || a->D > DNSPLAT_MAX_CHANNELS) return DNSPLAT_ERR_UNSUPPORTED;
     if (a->width <= 0 || a->height <= 0) return DNSPLAT_ERR_INVALID_ARG;
@@ -716,6 +738,11 @@ extern "C" int dnsplat_raster_bwd(const dnsplat_raster_args *a, dnsplat_stream_t
     ba.width = a->width; ba.height = a->height;
     ba.tw = dns_tiles_w(a->width, TILE);
     ba.n_tiles = ba.tw * dns_tiles_h(a->height, TILE);
+    ba.csx = csx; ba.csy = csy;
+    ba.ctw = (ba.tw + (1 << csx) - 1) >> csx;
+    ba.n_cells = ba.ctw * ((dns_tiles_h(a->height, TILE) + (1 << csy) - 1) >> csy);
+    ba.tile_boxes = (csx | csy) ? reinterpret_cast<const int2 *>(cells->tile_boxes) : nullptr;
+    if ((csx | csy) && !ba.tile_boxes && a->splats) return DNSPLAT_ERR_INVALID_ARG;      // like splats: NULL only where every list is empty
     ba.splats = reinterpret_cast<const float4 *>(a->splats);
     ba.flatten_ids = a->flatten_ids;
     ba.tile_offsets = a->tile_offsets;
@@ -744,6 +771,11 @@ extern "C" int dnsplat_raster_bwd(const dnsplat_raster_args *a, dnsplat_stream_t
         if (!dn->background_rgb || !dn->v_rgb || !dn->v_depth || !dn->v_normal || !a->render) return DNSPLAT_ERR_INVALID_ARG;
         ba.bg_rgb = dn->background_rgb; ba.dn_v_rgb = dn->v_rgb; ba.dn_v_depth = dn->v_depth;
         ba.dn_v_normal = dn->v_normal; ba.dn_v_acc = dn->v_accumulation;
+        if (csx | csy) {
+            if (ba.counters) return launch_bwd<7, 4, true, true, false, true>(ba, stream);
+            if (ba.keep_masks) return launch_bwd<7, 4, true, false, true, true>(ba, stream);
+            return launch_bwd<7, 4, true, false, false, true>(ba, stream);
+        }
         if (ba.counters) return launch_bwd<7, 4, true, true>(ba, stream);
         if (ba.keep_masks) return launch_bwd<7, 4, true, false, true>(ba, stream);
         return launch_bwd<7, 4, true>(ba, stream);

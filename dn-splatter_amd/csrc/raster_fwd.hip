@@ -81,6 +81,11 @@ struct FwdArgs {
     float *__restrict__ dn_depth_max;
     float4 *zero_fill;                         // dnsplat_raster_args.zero_fill: cleared by this launch, zero_fill_vec4 16-byte pieces
     long long zero_fill_vec4;
+    // list cells (DN instantiations only, dnsplat_raster_cells): the lists are per cell of 2^csx x 2^csy tiles, ctw cells per row and
+    // n_cells per camera.  csx == csy == 0: ctw == tw, n_cells == n_tiles, every tile is its own cell
+    int csx, csy, ctw, n_cells;
+    const int2 *__restrict__ tile_boxes;       // with cells: [entries] dnsplat_proj_out.tile_boxes — a tile takes a list entry only if the entry's
+                                               // own tile box holds the tile (dns_tile_in_box); NULL without cells
 };
 
 // The dn-splatter per-pixel post-ops (dn_model.py:526-528, 577-578) applied to one finished pixel.  bg_rgb: the background colour,
@@ -137,7 +142,9 @@ __device__ __forceinline__ float sel0(uint64_t mask, float a)
 // scalar FMAs, the odd channel as a pair): 45 instead of 46 vector and 21 instead of 23 scalar instructions in the loop, the hand-placed
 // exit unchanged, but two accumulator layouts live across the batch loop, 82 VGPRs instead of 66.  0.4549 vs 0.4548 ms in paired
 // replays (docs/history.md, section 22).  Not kept: this loop does not get faster by dropping instructions.)
-template <int D, bool DN, bool COUNT = false>
+// CELLS: the lists are per cell of several tiles (dnsplat_raster_cells; fused pass only).  Without it the kernel is the one it was before
+// cells existed, instruction for instruction.
+template <int D, bool DN, bool COUNT = false, bool CELLS = false>
 __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kernel(FwdArgs a)
 {
     // one 64-record slice per wave: [wave][splat][4 x float4]
@@ -156,11 +163,17 @@ __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kern
     const int cam = blockIdx.x / a.n_tiles;
     const int tile = dns_tile_of_block(blockIdx.x - cam * a.n_tiles, a.n_tiles, a.tw);
     const size_t img = (size_t)cam * a.width * a.height;
-    const int list = cam * a.n_tiles + tile;
     const int wave = threadIdx.x / DNS_WAVE;
     [[maybe_unused]] unsigned long long n_entries = 0, n_walked = 0, n_live = 0, n_blend = 0;
     const int lane = threadIdx.x & (DNS_WAVE - 1);
     const int tile_x = tile % a.tw, tile_y = tile / a.tw;
+    // the list this tile reads and the plane of the keep masks this half tile writes: its own list and its half, or (CELLS) the list
+    // of its cell and the half tile's position inside the cell
+    int list = cam * a.n_tiles + tile, plane = wave;
+    if (CELLS) {
+        list = cam * a.n_cells + (tile_y >> a.csy) * a.ctw + (tile_x >> a.csx);
+        plane = ((((tile_y & ((1 << a.csy) - 1)) << a.csx) | (tile_x & ((1 << a.csx) - 1))) << 1) | wave;
+    }
     const int px_i = tile_x * TILE + (lane & 15);
     const int py_i0 = tile_y * TILE + wave * 8 + (lane >> 4);
     const int py_i1 = py_i0 + 4;
@@ -198,10 +211,15 @@ __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kern
     float4 r0, r1, r2;
     [[maybe_unused]] float4 r3;
     [[maybe_unused]] float r3x = 0.f;
+    // list cells: the entry's own tile box, fetched beside its record
+    constexpr bool boxed = CELLS;
+    [[maybe_unused]] const float inv_tw = CELLS ? 1.f / (float)a.tw : 0.f;
+    [[maybe_unused]] int2 bx = make_int2(0, 0);
     {
         const int idx = range_start + lane;
         if (idx < range_end) {
             const int g = a.flatten_ids[idx];
+            if (boxed) bx = a.tile_boxes[g];
             const float4 *rec = a.splats + (size_t)g * 4;
             r0 = rec[0]; r1 = rec[1];
             if (D > 2) r2 = rec[2];
@@ -214,11 +232,11 @@ __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kern
         if ((done0 & done1) == ~0ull) break;
         // Splats that cannot reach alpha >= 1/255 anywhere in the half tile are dropped here, once per
         // (wave, splat), instead of being rejected 128 times by the per-pixel test.
-        const bool keep = (batch_start + lane < range_end) &&
+        const bool keep = (batch_start + lane < range_end) && (!boxed || dns_tile_in_box(bx, tile_x, tile_y, a.tw, inv_tw)) &&
                           !dns_cull_rect(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, rxl, rxh, ryl, ryh);
         uint64_t todo = dns_ballot(keep);
         if (a.keep_masks && lane == 0)
-            a.keep_masks[(size_t)wave * a.keep_mask_stride + (range_start >> 6) + list + ((batch_start - range_start) >> 6)] = todo;
+            a.keep_masks[(size_t)plane * a.keep_mask_stride + (range_start >> 6) + list + ((batch_start - range_start) >> 6)] = todo;
         if (COUNT) n_entries += min(DNS_WAVE, range_end - batch_start);
         // stage the prefetched records (waits for the gather here) with the conic pre-scaled for exp2,
         // then start the next gather
@@ -234,6 +252,7 @@ __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kern
             const int idx = batch_start + DNS_WAVE + lane;
             if (idx < range_end) {
                 const int g = a.flatten_ids[idx];
+                if (boxed) bx = a.tile_boxes[g];
                 const float4 *rec = a.splats + (size_t)g * 4;
                 r0 = rec[0]; r1 = rec[1];
                 if (D > 2) r2 = rec[2];
@@ -517,19 +536,24 @@ __global__ __launch_bounds__(FWD_THREADS) DNS_FWD_OCCUPANCY void raster_fwd_kern
     }
 }
 
-template <int D, bool DN = false, bool COUNT = false>
+template <int D, bool DN = false, bool COUNT = false, bool CELLS = false>
 int launch_fwd(const FwdArgs &fa, int n_cameras, hipStream_t stream)
 {
-    hipLaunchKernelGGL((raster_fwd_kernel<D, DN, COUNT>), dim3(fa.n_tiles * n_cameras), dim3(FWD_THREADS), 0, stream, fa);
+    hipLaunchKernelGGL((raster_fwd_kernel<D, DN, COUNT, CELLS>), dim3(fa.n_tiles * n_cameras), dim3(FWD_THREADS), 0, stream, fa);
     DNS_CHECK_LAUNCH();
     return DNSPLAT_OK;
 }
 
 }  // namespace
 
-extern "C" int dnsplat_raster_fwd(const dnsplat_raster_args *a, dnsplat_stream_t stream_)
+extern "C" int dnsplat_raster_fwd(const dnsplat_raster_args *a, dnsplat_stream_t stream) { return dnsplat_raster_fwd_cells(a, nullptr, stream); }
+
+extern "C" int dnsplat_raster_fwd_cells(const dnsplat_raster_args *a, const dnsplat_raster_cells *cells, dnsplat_stream_t stream_)
 {
     if (!a) return DNSPLAT_ERR_INVALID_ARG;
+    const int csx = cells ? cells->shift_x : 0, csy = cells ? cells->shift_y : 0;
+    if (csx < 0 || csx > 4 || csy < 0 || csy > 4) return DNSPLAT_ERR_INVALID_ARG;
+    if ((csx | csy) && !a->dn) return DNSPLAT_ERR_UNSUPPORTED;       // only the fused pass reads per-cell lists
     if (a->tile_size != TILE) return DNSPLAT_ERR_UNSUPPORTED;
     if (a->D < 1 || a->D > DNSPLAT_MAX_CHANNELS) return DNSPLAT_ERR_UNSUPPORTED;
     if (a->width <= 0 || a->height <= 0) return DNSPLAT_ERR_INVALID_ARG;
@@ -540,6 +564,11 @@ extern "C" int dnsplat_raster_fwd(const dnsplat_raster_args *a, dnsplat_stream_t
     fa.width = a->width; fa.height = a->height;
     fa.tw = dns_tiles_w(a->width, TILE);
     fa.n_tiles = fa.tw * dns_tiles_h(a->height, TILE);
+    fa.csx = csx; fa.csy = csy;
+    fa.ctw = (fa.tw + (1 << csx) - 1) >> csx;
+    fa.n_cells = fa.ctw * ((dns_tiles_h(a->height, TILE) + (1 << csy) - 1) >> csy);
+    fa.tile_boxes = (csx | csy) ? reinterpret_cast<const int2 *>(cells->tile_boxes) : nullptr;
+    if ((csx | csy) && !fa.tile_boxes && a->splats) return DNSPLAT_ERR_INVALID_ARG;      // like splats: NULL only where every list is empty
     fa.splats = reinterpret_cast<const float4 *>(a->splats);
     fa.flatten_ids = a->flatten_ids;
     fa.tile_offsets = a->tile_offsets;
@@ -563,6 +592,10 @@ extern "C" int dnsplat_raster_fwd(const dnsplat_raster_args *a, dnsplat_stream_t
         if (!dn->background_rgb || !dn->rgb || !dn->depth || !dn->normal || !dn->depth_max) return DNSPLAT_ERR_INVALID_ARG;
         fa.bg_rgb = dn->background_rgb; fa.dn_rgb = dn->rgb; fa.dn_depth = dn->depth; fa.dn_normal = dn->normal;
         fa.dn_depth_max = dn->depth_max;
+        if (csx | csy) {
+            if (fa.counters) return launch_fwd<7, true, true, true>(fa, C, stream);
+            return launch_fwd<7, true, false, true>(fa, C, stream);
+        }
         if (fa.counters) return launch_fwd<7, true, true>(fa, C, stream);
         return launch_fwd<7, true>(fa, C, stream);
     }

@@ -93,6 +93,26 @@ __device__ __forceinline__ void dns_snug_tile_bbox(float mx, float my, float ca,
 //   bands over a row-interleaved image (every XCD gets rows from the whole height)                     1.91
 // Both kernels are bound by vector instructions, not by L2 misses (0.2 TB/s of HBM traffic), so the L2 locality of the
 // bands buys nothing here and the finer interleave of the identity order balances the XCDs slightly better.
+// List cells (dnsplat_raster_cells): a cell's list holds every Gaussian whose tile box touches one of the cell's tiles, but a tile only
+// composites the Gaussians whose box holds the tile ITSELF — the box is clipped to gsplat's 3-sigma box (A.3), outside of which a
+// splat of opacity > 0.35 still reaches alpha >= 1/255 and the reference does not blend it.  b = the Gaussian's record of
+// dnsplat_proj_out.tile_boxes (first tile id within the camera's grid of tw columns, width | height << 16); inv_tw = 1.f / tw.
+// The row of the first tile through the fp32 reciprocal is at most one off below 2^24 tiles and is put right; beyond, by division.
+__device__ __forceinline__ bool dns_tile_in_box(int2 b, int tx, int ty, int tw, float inv_tw)
+{
+    int y0, x0;
+    if (b.x < (1 << 24)) {
+        y0 = (int)((float)b.x * inv_tw);
+        x0 = b.x - y0 * tw;
+        if (x0 < 0) { x0 += tw; --y0; }
+        else if (x0 >= tw) { x0 -= tw; ++y0; }
+    } else {
+        y0 = b.x / tw;
+        x0 = b.x - y0 * tw;
+    }
+    return (unsigned)(tx - x0) < ((unsigned)b.y & 0xffffu) && (unsigned)(ty - y0) < ((unsigned)b.y >> 16);
+}
+
 __device__ __forceinline__ int dns_tile_of_block(int b, int n_tiles, int tw)
 {
     return b;

@@ -163,7 +163,11 @@ def _render_dn_batch(means, quats, scales, opacities, features_dc, features_rest
     rgb, depth, normal, acc, surface_normal = _ops.rasterize_dn(
         pr["means2d"], pr["splats"], pr["depths"], pr["radii"], pr["tiles_bin"], background_rgb=background_rgb,
         width=width, height=height, intrinsics=intr, absgrad=absgrad, holder=holder, tight=pr["tight_tiles"], tile_boxes=pr["tile_boxes"])
-    b = holder["binning"]
+    # The kernels' lists may be per cell of several tiles (_ops.BIN_CELL); everything below that speaks of tile lists shows the per-tile
+    # ones — the count comes with the frame, the lists are sorted when somebody reads them (_ops._PerTileLists)
+    cell_lists = holder["binning"]
+    b = holder.get("tile_lists", cell_lists)
+    sx, sy = cell_lists.cells or (0, 0)
     info = _ops.LazyInfo({
         "means2d": pr["means2d"], "radii": pr["radii"], "depths": pr["depths"], "conics": pr["conics"],
         # tiles_per_gauss: gsplat's count (what dn_model.py:524 stores as num_tiles_hit); tiles_bin: the count this path's binning
@@ -173,8 +177,11 @@ def _render_dn_batch(means, quats, scales, opacities, features_dc, features_rest
         "tile_width": b.tile_width, "tile_height": b.tile_height,
         "width": width, "height": height, "tile_size": 16, "n_cameras": C, "_binning": b, "tight_tiles": cfg.tight_tiles,
         "_saturation_flag": saturation_flag,
+        "cell_shape": (1 << sx, 1 << sy),      # tiles per list cell of the kernels' own lists (1 x 1: one list per tile)
+        "_cell_lists": cell_lists,             # those lists themselves (a handle for tests and tools, like _binning)
     }, lazy={     # need the intersection count on the host: under the "deferred" bin policy reading them is what waits for it
         "flatten_ids": lambda: b.flatten_ids[: b.n_isects], "n_isects": lambda: b.n_isects,
+        "n_cell_pairs": lambda: cell_lists.n_isects,      # entries of the kernels' own lists (== n_isects with 1 x 1 cells)
         # this path keeps [start, end) per tile; gsplat's offsets of the empty tiles are filled in when somebody asks
         "isect_offsets": lambda: b.filled_offsets()[:-1].reshape(C, b.tile_height, b.tile_width),
     })

@@ -68,7 +68,9 @@ extern "C" {
  * dnsplat_tsdf_integrate / dnsplat_tsdf_args / dnsplat_tsdf_vertex_colors / dnsplat_mc_observed_scratch_bytes /
  * dnsplat_mc_count_observed / dnsplat_mc_emit_observed / dnsplat_mc_observed_args: TSDF fusion and the mesh of what was observed;
  * dnsplat_mesh_clusters / dnsplat_mesh_clusters_scratch_bytes / dnsplat_mesh_clusters_args / dnsplat_mesh_filter_scratch_bytes /
- * dnsplat_mesh_filter_count / dnsplat_mesh_filter_emit / dnsplat_mesh_filter_args: the connected-component filter behind that mesh). */
+ * dnsplat_mesh_filter_count / dnsplat_mesh_filter_emit / dnsplat_mesh_filter_args: the connected-component filter behind that mesh;
+ * dnsplat_bin_prepare_cells / dnsplat_bin_emit_sort_cells / dnsplat_bin_cells / dnsplat_raster_fwd_cells / dnsplat_raster_bwd_cells /
+ * dnsplat_raster_cells / dnsplat_det_reduce_planes: the fused path's tile lists kept per cell of several tiles). */
 #define DNSPLAT_ABI_VERSION 15
 #define DNSPLAT_RECORD_FLOATS 16
 #define DNSPLAT_MAX_CHANNELS 8
@@ -232,6 +234,28 @@ int dnsplat_bin_emit_sort(const dnsplat_bin_args *args, dnsplat_stream_t stream)
 int dnsplat_bin_isect_ids(int32_t n_tiles, int32_t n_cameras, const int32_t *tile_offsets, const int32_t *flatten_ids,
                           const float *depths, int64_t *isect_ids, int64_t capacity, dnsplat_stream_t stream);
 
+/* List cells (added after ABI 15, found by symbol).  dnsplat_bin_prepare_cells / dnsplat_bin_emit_sort_cells are dnsplat_bin_prepare /
+ * dnsplat_bin_emit_sort with ONE SORTED LIST PER CELL of 2^shift_x x 2^shift_y tiles instead of one per tile; cells == NULL (or both
+ * shifts 0 and no n_tile_pairs) is exactly the call without the suffix.  A consumer that re-tests every list entry against its own
+ * part of the tile anyway (the fused compositing kernels: dnsplat_raster_fwd_cells / dnsplat_raster_bwd_cells) loses nothing by a
+ * coarser list and the tile sort handles a Gaussian once per cell instead of once per tile.  The tile box [x0, x1) x [y0, y1) of a Gaussian
+ * becomes the cell box [x0 >> shift_x, ((x1 - 1) >> shift_x) + 1) x [y0 >> shift_y, ((y1 - 1) >> shift_y) + 1) of a grid of
+ * ceil(tiles_w / 2^shift_x) x ceil(tiles_h / 2^shift_y) cells per camera (the cell grids of a batch are stacked like its tile grids).
+ * The list of a cell is the depth-ordered union of the lists its tiles would have had, every Gaussian once.  With cells
+ *   - dnsplat_bin_args.tile_boxes is required (the cells are cut out of the projection's boxes; tiles_per_gauss is not read);
+ *   - tile_offsets [n_cameras * n_cells + 1], tile_ends [n_cameras * n_cells] and flatten_ids are per cell; n_isects, isect_capacity
+ *     and n_isects_host count (cell, Gaussian) pairs;
+ *   - n_tile_pairs receives what n_isects would have been without cells, sum(width x height) over the boxes. */
+typedef struct dnsplat_bin_cells {
+    int32_t shift_x, shift_y;   /* 0..4 each */
+    int64_t *n_tile_pairs;      /* optional device scalar.  If it is given together with dnsplat_bin_args.n_isects_host it must be
+                                   n_isects + 1, and n_isects_host receives both words in one copy */
+    int64_t *n_tile_pairs_max;  /* optional device scalar the caller zeroes once: running maximum of n_tile_pairs, as
+                                   dnsplat_bin_args.n_isects_max is of n_isects (here: of the cell pairs) */
+} dnsplat_bin_cells;
+int dnsplat_bin_prepare_cells(const dnsplat_bin_args *args, const dnsplat_bin_cells *cells, dnsplat_stream_t stream);
+int dnsplat_bin_emit_sort_cells(const dnsplat_bin_args *args, const dnsplat_bin_cells *cells, dnsplat_stream_t stream);
+
 /* ------------------------------------------------------------------ stage 3/4
  * Per-tile front-to-back alpha compositing of D feature channels (A6 + A8 in one
  * pass) and its backward. */
@@ -308,6 +332,26 @@ typedef struct dnsplat_raster_args {
 int dnsplat_raster_fwd(const dnsplat_raster_args *args, dnsplat_stream_t stream);
 int dnsplat_raster_bwd(const dnsplat_raster_args *args, dnsplat_stream_t stream);
 
+/* The fused pass (args->dn != NULL) over the per-cell lists of dnsplat_bin_emit_sort_cells (added after ABI 15, found by symbol);
+ * cells == NULL or both shifts 0 is the call without the suffix.  The list of a tile is the list of the cell it lies in: every 16x8
+ * half tile takes it in batches of 64, runs its rectangle test on every entry and walks the survivors, as it does with a per-tile
+ * list — entries whose own tile box leaves this tile out are dropped with the culled ones (dnsplat_raster_cells.tile_boxes), so the
+ * splats a tile walks, their order and the images are the per-tile ones bit for bit.  With cells
+ *   - tile_offsets / tile_ends / flatten_ids are per cell, last_ids are positions in the cell lists;
+ *   - a half tile has a PLANE: p = ((tile_y & (2^shift_y - 1)) << shift_x | (tile_x & (2^shift_x - 1))) * 2 + half, one of
+ *     P = 2 * 2^shift_x * 2^shift_y.  keep_masks is [P * keep_mask_stride], the word of (list l = camera * n_cells + cell, plane p,
+ *     batch b) is [p * stride + (tile_offsets[l] >> 6) + l + b], keep_mask_stride >= (capacity >> 6) + n_cameras * n_cells + 1;
+ *   - det_partials is [P, det_capacity, 16], the row of (plane p, list index i) at [p][i][:]; dnsplat_det_reduce_planes adds them up. */
+typedef struct dnsplat_raster_cells {
+    int32_t shift_x, shift_y;   /* as dnsplat_bin_cells */
+    const int32_t *tile_boxes;  /* [entries, 2] dnsplat_bin_args.tile_boxes of the binning behind the lists (required with a nonzero shift).  A
+                                   tile takes a list entry only if the entry's OWN tile box holds the tile: the box is clipped to gsplat's
+                                   3-sigma box, beyond which a splat of opacity > 0.35 would still pass the alpha test — per-tile lists never
+                                   hold it there, and neither may a cell's */
+} dnsplat_raster_cells;
+int dnsplat_raster_fwd_cells(const dnsplat_raster_args *args, const dnsplat_raster_cells *cells, dnsplat_stream_t stream);
+int dnsplat_raster_bwd_cells(const dnsplat_raster_args *args, const dnsplat_raster_cells *cells, dnsplat_stream_t stream);
+
 /* Deterministic reduction of the rows dnsplat_raster_bwd left in det_partials (test / debug mode, DNSPLAT_DETERMINISTIC=1 in the
  * Python binding): the sorted list is stably re-sorted by record id (hand-written LSD radix, as the binning), and each record g
  * that has list entries receives
@@ -326,6 +370,9 @@ typedef struct dnsplat_det_args {
 } dnsplat_det_args;
 size_t dnsplat_det_workspace_bytes(int64_t capacity);
 int dnsplat_det_reduce(const dnsplat_det_args *args, dnsplat_stream_t stream);
+/* dnsplat_det_reduce over `partials` [n_planes, capacity, 16] (added after ABI 15, found by symbol; dnsplat_raster_bwd_cells): per entry
+ * the planes in ascending order.  n_planes == 2 is dnsplat_det_reduce. */
+int dnsplat_det_reduce_planes(const dnsplat_det_args *args, int32_t n_planes, dnsplat_stream_t stream);
 
 /* Depth fill + depth->normal stencil of get_outputs (dn_model.py:533-537 and 589-603 with
  * utils/normal_utils.py:9-48, utils/camera_utils.py:92-144, called with c2w = identity):
