@@ -41,6 +41,8 @@ from . import tsdf, torch_tsdf  # noqa: F401
 from .tsdf import TSDFVolume, fuse_tsdf_mesh  # noqa: F401
 from . import mesh_clusters, torch_mesh_clusters  # noqa: F401
 from .mesh_clusters import cluster_connected_triangles, filter_small_clusters  # noqa: F401
+from . import cloud_filter, torch_cloud_filter  # noqa: F401
+from .cloud_filter import remove_statistical_outlier, voxel_down_sample  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -56,5 +58,6 @@ __all__ = [
     "mesh_cull", "torch_mesh_cull", "cull_mesh", "culled_mesh_metrics", "cut_mesh", "render_mesh_depth", "vertex_visibility",
     "tsdf", "torch_tsdf", "TSDFVolume", "fuse_tsdf_mesh",
     "mesh_clusters", "torch_mesh_clusters", "cluster_connected_triangles", "filter_small_clusters",
+    "cloud_filter", "torch_cloud_filter", "remove_statistical_outlier", "voxel_down_sample",
     "build_library", "load_library", "DnsplatError",
 ]

@@ -281,6 +281,21 @@ class MeshFilterArgs(ctypes.Structure):
     ]
 
 
+class CloudOutlierArgs(ctypes.Structure):
+    _fields_ = [
+        ("N", c_int32), ("nb_neighbors", c_int32), ("points", c_void_p), ("index", c_void_p), ("std_ratio", ctypes.c_double),
+        ("scratch", c_void_p), ("scratch_bytes", c_size_t), ("avg", c_void_p), ("stats", c_void_p), ("capacity", c_int64), ("ind", c_void_p),
+    ]
+
+
+class VoxelArgs(ctypes.Structure):
+    _fields_ = [
+        ("N", c_int32), ("points", c_void_p), ("normals", c_void_p), ("colors", c_void_p), ("voxel_size", ctypes.c_double),
+        ("scratch", c_void_p), ("scratch_bytes", c_size_t), ("counts", c_void_p), ("voxel_of", c_void_p), ("cap_v", c_int64),
+        ("out_points", c_void_p), ("out_normals", c_void_p), ("out_colors", c_void_p), ("out_counts", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -320,6 +335,9 @@ EXPORTS = [
     # likewise: the connected-component filter of a mesh (clusters of triangles, the small ones cut)
     "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_clusters", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_mesh_filter_count",
     "dnsplat_mesh_filter_emit",
+    # likewise: the point-cloud filters (statistical outlier removal, voxel down-sampling)
+    "dnsplat_cloud_outlier_scratch_bytes", "dnsplat_cloud_neighbor_mean", "dnsplat_cloud_outlier_stats", "dnsplat_cloud_outlier_count",
+    "dnsplat_cloud_outlier_emit", "dnsplat_voxel_scratch_bytes", "dnsplat_voxel_count", "dnsplat_voxel_emit",
     # likewise: the fused path's tile lists per cell of several tiles
     "dnsplat_bin_prepare_cells", "dnsplat_bin_emit_sort_cells", "dnsplat_raster_fwd_cells", "dnsplat_raster_bwd_cells",
     "dnsplat_det_reduce_planes",
@@ -457,13 +475,22 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_mesh_filter_scratch_bytes.argtypes = [c_int32, c_int32]
         L.dnsplat_mesh_filter_count.argtypes = [ctypes.POINTER(MeshFilterArgs), c_void_p]
         L.dnsplat_mesh_filter_emit.argtypes = [ctypes.POINTER(MeshFilterArgs), c_void_p]
+        L.dnsplat_cloud_outlier_scratch_bytes.restype = c_size_t
+        L.dnsplat_cloud_outlier_scratch_bytes.argtypes = [c_int32]
+        for fn in (L.dnsplat_cloud_neighbor_mean, L.dnsplat_cloud_outlier_stats, L.dnsplat_cloud_outlier_count, L.dnsplat_cloud_outlier_emit):
+            fn.argtypes = [ctypes.POINTER(CloudOutlierArgs), c_void_p]
+        L.dnsplat_voxel_scratch_bytes.restype = c_size_t
+        L.dnsplat_voxel_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_voxel_count.argtypes = [ctypes.POINTER(VoxelArgs), c_void_p]
+        L.dnsplat_voxel_emit.argtypes = [ctypes.POINTER(VoxelArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
                             "dnsplat_pointcloud_scratch_bytes", "dnsplat_eval_metrics_scratch_bytes", "dnsplat_knn_grid_dim",
                             "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
                             "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes",
-                            "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_filter_scratch_bytes"):
+                            "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_cloud_outlier_scratch_bytes",
+                            "dnsplat_voxel_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, VoxelArgs, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -561,6 +561,31 @@ def _mesh_filter_args(n_vertices, triangles, labels, sizes, cluster_counts, keep
     a.cap_v = 0 if vertex_index is None else vertex_index.shape[0]
     a.cap_t = 0 if out_triangles is None else out_triangles.shape[0]
     a.vertex_index, a.out_triangles, a.status = _ptr(vertex_index), _ptr(out_triangles), _ptr(status)
+    return a
+
+
+def _cloud_outlier_args(points, index, nb_neighbors, std_ratio, scratch, avg, stats, ind=None):
+    a = CloudOutlierArgs()
+    a.N, a.nb_neighbors = avg.shape[0], nb_neighbors
+    a.points, a.index = _ptr(points), _ptr(index)
+    a.std_ratio = std_ratio
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.avg, a.stats = _ptr(avg), _ptr(stats)
+    a.capacity = 0 if ind is None else ind.shape[0]
+    a.ind = _ptr(ind)
+    return a
+
+
+def _voxel_args(points, normals, colors, voxel_size, scratch, counts, voxel_of, out_points=None, out_normals=None, out_colors=None,
+                out_counts=None):
+    a = VoxelArgs()
+    a.N = points.shape[0]
+    a.points, a.normals, a.colors = _ptr(points), _ptr(normals), _ptr(colors)
+    a.voxel_size = voxel_size
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.counts, a.voxel_of = _ptr(counts), _ptr(voxel_of)
+    a.cap_v = 0 if out_points is None else out_points.shape[0]
+    a.out_points, a.out_normals, a.out_colors, a.out_counts = _ptr(out_points), _ptr(out_normals), _ptr(out_colors), _ptr(out_counts)
     return a
 
 

@@ -286,6 +286,17 @@ class AppendBuffers:
         return cursor
 
 
+def _without_outliers(cloud, std_ratio: float):
+    """The arrays of ``cloud`` (same rows) gathered with the ``ind`` of the statistical outlier filter over the first; an empty cloud
+    passes through."""
+    from .cloud_filter import remove_statistical_outlier
+
+    if cloud[0].shape[0] == 0:
+        return cloud
+    ind, _ = remove_statistical_outlier(cloud[0], nb_neighbors=20, std_ratio=std_ratio)
+    return tuple(x.index_select(0, ind) for x in cloud)
+
+
 class OrientedPointCloud(AppendBuffers):
     """Caller-sized buffers of points, normals and colours that ``add_frame`` appends to on the device.
 
@@ -338,20 +349,25 @@ class OrientedPointCloud(AppendBuffers):
                            normals=self.normals, state=self.state, surface_normal=surface_normal, mask=mask, indices=indices,
                            counts=counts, crop_box=crop_box, scratch=scratch)
 
-    def finish(self) -> Tuple[Tensor, Tensor, Tensor]:
+    def finish(self, outlier_removal: bool = False, std_ratio: float = 2.0) -> Tuple[Tensor, Tensor, Tensor]:
         """(points, normals, colors) trimmed to the rows appended so far.  Synchronises; raises ``DnsplatError`` if the buffers were
-        too small for what the frames produced or an index lay outside its frame."""
+        too small for what the frames produced or an index lay outside its frame.  ``outlier_removal`` is the exporter's switch
+        (export_mesh.py:487-491): the three arrays gathered with the ``ind`` of
+        ``cloud_filter.remove_statistical_outlier(points, nb_neighbors=20, std_ratio=std_ratio)``."""
         cursor = self._cursor(self.state.tolist(),
                               f"OrientedPointCloud overflow: the frames produced more than capacity = {self.capacity} points",
                               "OrientedPointCloud: an index passed to add_frame lies outside its frame")
-        return self.points[:cursor], self.normals[:cursor], self.colors[:cursor]
+        cloud = self.points[:cursor], self.normals[:cursor], self.colors[:cursor]
+        return _without_outliers(cloud, std_ratio) if outlier_removal else cloud
 
 
 def export_oriented_points(renderer, cameras, total_points: int = 2_000_000, *, filter_edges: bool = False, edge_threshold: float = 0.004,
-                           edge_dilation_iterations: int = 10, crop_box=None, masks=None, seed: int = 0, max_batch: int = 8):
+                           edge_dilation_iterations: int = 10, crop_box=None, masks=None, seed: int = 0, max_batch: int = 8,
+                           outlier_removal: bool = False, std_ratio: float = 2.0):
     """The loop of ``DepthAndNormalMapsPoisson.main`` (export_mesh.py:351-476): ``samples_per_frame = (total_points + F) // F`` pixels
     of each of the F ``cameras``, rendered through ``renderer.get_outputs_batch``; frame f draws with seed ``seed + f`` and uses
-    ``masks[f]`` if ``masks`` is given.  Returns (points, normals, colors), [n,3] each, on the device."""
+    ``masks[f]`` if ``masks`` is given.  ``outlier_removal`` / ``std_ratio``: the statistical outlier filter of :487-491 on the finished
+    cloud (``OrientedPointCloud.finish``).  Returns (points, normals, colors), [n,3] each, on the device."""
     F_ = len(cameras)
     if F_ == 0:
         raise ValueError("export_oriented_points needs at least one camera")
@@ -366,4 +382,4 @@ def export_oriented_points(renderer, cameras, total_points: int = 2_000_000, *, 
             cloud.add_frame(out, chunk[j], samples_per_frame=samples_per_frame, filter_edges=filter_edges, edge_threshold=edge_threshold,
                             edge_dilation_iterations=edge_dilation_iterations, mask=None if masks is None else masks[f], crop_box=crop_box,
                             seed=seed + f)
-    return cloud.finish()
+    return cloud.finish(outlier_removal=outlier_removal, std_ratio=std_ratio)

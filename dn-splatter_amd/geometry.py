@@ -119,9 +119,19 @@ def cloud_distances(src, tgt, src_normals=None, tgt_normals=None, threshold: flo
     return CloudDistances(dist2, idx, absdot, scalars, counts)
 
 
-def calculate_accuracy(reconstructed_points, reference_points, percentile=90) -> Tensor:
+def _down_sampled(points, voxel_size, name: str) -> Tensor:
+    """eval_pd.py:82: ``pcd.voxel_down_sample(voxel_size)`` — the voxel means, rounded to float32 once like every cloud here."""
+    from .cloud_filter import voxel_down_sample
+
+    return voxel_down_sample(_device_points(points, name), voxel_size)[0].to(torch.float32)
+
+
+def calculate_accuracy(reconstructed_points, reference_points, percentile=90, down_sample_voxel: Optional[float] = None) -> Tensor:
     """metrics.py:39-45: how far ``percentile`` % of the reconstructed points are from the reference cloud — numpy's percentile of the
-    nearest-neighbour distances, a 0-dim float64 device tensor.  ``reference_points`` may be a ``KnnIndex``."""
+    nearest-neighbour distances, a 0-dim float64 device tensor.  ``reference_points`` may be a ``KnnIndex``.  ``down_sample_voxel``
+    (eval_pd.py:82: 0.01) first replaces the reconstructed cloud by ``cloud_filter.voxel_down_sample`` of it; None leaves it alone."""
+    if down_sample_voxel is not None:
+        reconstructed_points = _down_sampled(reconstructed_points, down_sample_voxel, "reconstructed_points")
     return cloud_distances(reconstructed_points, reference_points, percentile=float(percentile), with_idx=False).scalar("percentile")
 
 
@@ -133,16 +143,20 @@ def calculate_completeness(reconstructed_points, reference_points, threshold=0.0
 
 class PDMetrics(torch.nn.Module):
     """Drop-in for ``dn_splatter.metrics.PDMetrics``: ``forward(pred, gt) -> (acc, comp)`` on anything with ``.points``, arrays or device
-    tensors; 0-dim float64 device tensors, so the pipeline's ``.item()`` works."""
+    tensors; 0-dim float64 device tensors, so the pipeline's ``.item()`` works.  ``down_sample_voxel`` (eval_pd.py:82 passes 0.01 to
+    Open3D) down-samples the reconstructed cloud, and only it, before both scores; None, the default, scores the clouds as given."""
 
-    def __init__(self, **kwargs):
+    def __init__(self, down_sample_voxel: Optional[float] = None, **kwargs):
         super().__init__()
         self.acc = calculate_accuracy
         self.cmp = calculate_completeness
+        self.down_sample_voxel = down_sample_voxel
 
     @torch.no_grad()
     def forward(self, pred, gt):
         pred_points, gt_points = _device_points(pred, "pred"), _device_points(gt, "gt")
+        if self.down_sample_voxel is not None:
+            pred_points = _down_sampled(pred_points, self.down_sample_voxel, "pred")
         return self.acc(pred_points, gt_points), self.cmp(pred_points, gt_points)
 
 

@@ -31,8 +31,8 @@ from . import torch_levelset
 from ._lib import DnsplatError
 from ._ops import _f32c, _level_points_args, _level_rays_args, _need_gpu, _stream
 from .density import GaussianDensityField, _model_field
-from .export import (MAX_PIXELS, AppendBuffers, _bytes2d, _check_append_buffers, _crop, _export_c2w, _image2d, _scratch, _xform,
-                     sample_valid_pixels)
+from .export import (MAX_PIXELS, AppendBuffers, _bytes2d, _check_append_buffers, _crop, _export_c2w, _image2d, _scratch, _without_outliers,
+                     _xform, sample_valid_pixels)
 from .torch_density import KNN, SKIP
 
 RANGE_POINTS = 21           # include/dnsplat.h DNSPLAT_LEVEL_RANGE_POINTS
@@ -190,14 +190,18 @@ class LevelSetCloud(AppendBuffers):
                          points=self.points[l], colors=self.colors[l], normals=self.normals[l], state=self.state[l], gauss_normals=normals,
                          mask=mask, return_normal=return_normal, crop_box=crop_box, scratch=scratch, frame=frame)
 
-    def finish(self) -> dict:
+    def finish(self, outlier_removal: bool = False, std_ratio: float = 2.0) -> dict:
         """{level: {"points", "normals", "colors"}} trimmed to the rows appended so far.  Synchronises; raises ``DnsplatError`` if a
-        buffer was too small for what the frames produced."""
+        buffer was too small for what the frames produced.  ``outlier_removal`` is the exporter's switch (export_mesh.py:640): per
+        level, the three arrays gathered with the ``ind`` of ``cloud_filter.remove_statistical_outlier(points, 20, std_ratio)``."""
         result = {}
         for l, (level, row) in enumerate(zip(self.levels, self.state.tolist())):
             cursor = self._cursor(row, f"LevelSetCloud overflow: level {level} produced more than capacity = {self.capacity} points",
                                   "LevelSetCloud: an index lies outside its frame")
-            result[level] = {"points": self.points[l, :cursor], "normals": self.normals[l, :cursor], "colors": self.colors[l, :cursor]}
+            cloud = self.points[l, :cursor], self.normals[l, :cursor], self.colors[l, :cursor]
+            if outlier_removal:
+                cloud = _without_outliers(cloud, std_ratio)
+            result[level] = {"points": cloud[0], "normals": cloud[1], "colors": cloud[2]}
         return result
 
 
@@ -216,11 +220,12 @@ def level_surface_points(field: GaussianDensityField, outputs, camera, num_sampl
 
 def export_level_set_points(renderer, cameras, total_points: int = 2_000_000, *, field: Optional[GaussianDensityField] = None,
                             surface_levels: Sequence[float] = (0.1, 0.3, 0.5), return_normal: str = "closest_gaussian", crop_box=None,
-                            masks=None, seed: int = 0, max_batch: int = 8) -> dict:
+                            masks=None, seed: int = 0, max_batch: int = 8, outlier_removal: bool = False, std_ratio: float = 2.0) -> dict:
     """The camera loop of ``LevelSetExtractor.main`` (export_mesh.py:560-620): ``samples_per_frame = (total_points + F) // F`` hits per
     level of each of the F ``cameras``, rendered through ``renderer.get_outputs_batch``; frame f draws with seed ``seed + f`` and uses
-    ``masks[f]`` if ``masks`` is given.  ``field`` defaults to a snapshot of ``renderer.gauss_params``.  Returns {level: {"points",
-    "normals", "colors"}} on the device."""
+    ``masks[f]`` if ``masks`` is given.  ``field`` defaults to a snapshot of ``renderer.gauss_params``.  ``outlier_removal`` /
+    ``std_ratio``: the statistical outlier filter of :640 on each level's finished cloud.  Returns {level: {"points", "normals",
+    "colors"}} on the device."""
     F_ = len(cameras)
     if F_ == 0:
         raise ValueError("export_level_set_points needs at least one camera")
@@ -238,7 +243,7 @@ def export_level_set_points(renderer, cameras, total_points: int = 2_000_000, *,
             f = i + j
             cloud.add_frame(field, out, chunk[j], num_samples=samples_per_frame, normals=gp.get("normals"),
                             mask=None if masks is None else masks[f], return_normal=return_normal, seed=seed + f, crop_box=crop_box)
-    return cloud.finish()
+    return cloud.finish(outlier_removal=outlier_removal, std_ratio=std_ratio)
 
 
 _CALLS = "_dnsplat_level_set_calls"

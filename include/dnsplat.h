@@ -69,6 +69,9 @@ extern "C" {
  * dnsplat_mc_count_observed / dnsplat_mc_emit_observed / dnsplat_mc_observed_args: TSDF fusion and the mesh of what was observed;
  * dnsplat_mesh_clusters / dnsplat_mesh_clusters_scratch_bytes / dnsplat_mesh_clusters_args / dnsplat_mesh_filter_scratch_bytes /
  * dnsplat_mesh_filter_count / dnsplat_mesh_filter_emit / dnsplat_mesh_filter_args: the connected-component filter behind that mesh;
+ * dnsplat_cloud_outlier_scratch_bytes / dnsplat_cloud_neighbor_mean / dnsplat_cloud_outlier_stats / dnsplat_cloud_outlier_count /
+ * dnsplat_cloud_outlier_emit / dnsplat_cloud_outlier_args / dnsplat_voxel_scratch_bytes / dnsplat_voxel_count / dnsplat_voxel_emit /
+ * dnsplat_voxel_args: the point-cloud filters (statistical outlier removal, voxel down-sampling);
  * dnsplat_bin_prepare_cells / dnsplat_bin_emit_sort_cells / dnsplat_bin_cells / dnsplat_raster_fwd_cells / dnsplat_raster_bwd_cells /
  * dnsplat_raster_cells / dnsplat_det_reduce_planes: the fused path's tile lists kept per cell of several tiles). */
 #define DNSPLAT_ABI_VERSION 15
@@ -1288,6 +1291,102 @@ int dnsplat_mesh_clusters(const dnsplat_mesh_clusters_args *args, dnsplat_stream
 size_t dnsplat_mesh_filter_scratch_bytes(int32_t V, int32_t T);     /* 0 for an invalid size */
 int dnsplat_mesh_filter_count(const dnsplat_mesh_filter_args *args, dnsplat_stream_t stream);
 int dnsplat_mesh_filter_emit(const dnsplat_mesh_filter_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ point-cloud filters (added after ABI 15, found by symbol)
+ * The two Open3D filters the reference runs on the CPU between the clouds and their consumers: remove_statistical_outlier(
+ * nb_neighbors = 20, std_ratio), the last step before the solver of GaussiansToPoisson, DepthAndNormalMapsPoisson and LevelSetExtractor
+ * (export_mesh.py:287-291, :487-491, :640), and voxel_down_sample(voxel_size) (eval_pd.py:82 before calculate_accuracy /
+ * calculate_completeness; export_mesh.py:284-285).  Open3D is not at hand: both rules are restated from memory of
+ * PointCloud::RemoveStatisticalOutliers and PointCloud::VoxelDownSample, THEY ARE THIS PROJECT'S DEFINITION, PARITY UNPINNED AGAINST Open3D.
+ * Everything is caller-allocated; nothing is read on the host, allocated or synchronised; no floating-point atomic: equal inputs give
+ * equal bytes.
+ *
+ * STATISTICAL OUTLIER REMOVAL of points fp32 [N,3] with `index` = dnsplat_knn_build over the SAME points.  K = min(nb_neighbors, N).
+ *   avg        avg[i] = (sqrt(d2_0) + sqrt(d2_1) + ... + sqrt(d2_{K-1})) / K over the K nearest points under dnsplat_knn_query's key
+ *              (d2, index) with d2 in double — the point itself included, so the first term is 0 — the square roots in double and
+ *              correctly rounded (IEEE), added in ascending rank from 0.  A row with a non-finite coordinate gets avg = -1: it is not valid, nobody's neighbour and never
+ *              kept.  With fewer than K comparable points the missing ranks have d2 = inf.
+ *   moments    n_valid = the rows with avg >= 0 (those that were searched); sum = the sum of avg over avg > 0; mean = sum / n_valid;
+ *              std = sqrt((the sum of (avg - mean)^2 over avg > 0) / (n_valid - 1)); threshold = mean + std_ratio * std.  Two folds in
+ *              double in the one fixed order of the score kernels (per block of 256 rows, then the partials), the second after the first
+ *              has finished, as Open3D's two passes.  With n_valid <= 1: std = 0 and threshold = 0 (mean = 0 with n_valid = 0).
+ *   kept       row i iff avg[i] > 0 && avg[i] < threshold.  The kept indices ascend: Open3D's `ind`.
+ * dnsplat_cloud_neighbor_mean — avg double [N].  One launch, one thread per point.  nb_neighbors < 1: DNSPLAT_ERR_INVALID_ARG; above
+ *   DNSPLAT_KNN_MAX_K: DNSPLAT_ERR_UNSUPPORTED.
+ * dnsplat_cloud_outlier_stats — from avg (any double [N] under the conventions above): the record `stats`, device, 64 bytes, 8-byte
+ *   aligned: double {mean, std, threshold, sum}, int64 {n_valid, n_kept, 0, 0}.  n_kept is written 0.  Four launches.
+ * dnsplat_cloud_outlier_count — stats.n_kept, and the scanned kept rows per block in scratch; threshold is read on the device.  Two launches.
+ * dnsplat_cloud_outlier_emit — after count with the same arguments: ind int64, the first min(n_kept, capacity) kept indices, nothing past
+ *   the capacity.  One launch; it may be repeated.
+ * scratch: dnsplat_cloud_outlier_scratch_bytes(N) bytes, 8-byte aligned (36 per 256 points; 0 for N < 1); neighbor_mean needs none.
+ * All four return without touching the device: DNSPLAT_ERR_INVALID_ARG for a NULL args or a NULL required pointer, N < 1, a nan
+ * std_ratio (stats), a negative capacity or a positive one without ind (emit); DNSPLAT_ERR_WORKSPACE for a short or misaligned scratch.
+ *
+ * VOXEL DOWN-SAMPLING of points fp32 [N,3] with optional normals and colors fp32 [N,3]; all arithmetic in double.
+ *   voxel      lo[a] = min_i p[i][a] - voxel_size / 2;  ref = (p - lo) / voxel_size;  idx = floor(ref) per axis.  idx[a] >= 2^21 sets
+ *              DNSPLAT_VOXEL_STATUS_EXTENT (the three indices pack into one 63-bit key), a non-finite coordinate
+ *              DNSPLAT_VOXEL_STATUS_NONFINITE.
+ *   order      voxels are numbered in order of first appearance: v precedes w iff its lowest point index is lower.  (Open3D's order is
+ *              that of a hash map.)
+ *   mean       an exact integer sum: a position adds q = llrint((ref - idx) * 2^31) per axis to an int64 S, the voxel's n points are
+ *              counted, and p' = (lo + idx * voxel_size) + (voxel_size * ((double)S / n)) / 2^31.  A normal or colour component c adds
+ *              llrint(c * 2^30); |c| > 2 or a nan sets DNSPLAT_VOXEL_STATUS_ATTRIBUTE; the mean is ((double)S / n) / 2^30, NOT
+ *              re-normalised, as in Open3D.  With N < 2^31 no sum overflows.
+ * dnsplat_voxel_count — counts device int64 [2] = {V, status} and voxel_of int32 [N], the voxel of each point (-1 for a row that has
+ *   none under a non-zero status; the outputs mean nothing then).  An open-addressing table of 2 N slots (64-bit keys claimed by
+ *   compare-and-swap, each voxel's lowest point by an integer minimum), a flag-and-scan over the points that numbers the voxels, integer
+ *   sums per voxel — added once per voxel per wave where lanes share one.  Every probe is bounded by the table;
+ *   DNSPLAT_VOXEL_STATUS_INTERNAL if one ran out, which cannot happen on a correct build.  Eight launches.
+ * dnsplat_voxel_emit — after count with the same arguments: the first min(V, cap_v) rows of out_points / out_normals / out_colors double
+ *   [cap_v,3] and out_counts int32 [cap_v] (may be NULL).  One launch; it may be repeated.
+ * scratch: dnsplat_voxel_scratch_bytes(N, the number of attribute arrays) bytes, 8-byte aligned: 32 + 28 N + 8 (4 + 3 attributes) N +
+ *   4 per 256 points + 3072; 0 for N < 1, N > (2^31 - 1) / 2 or attributes outside [0, 2].
+ * Both return without touching the device: DNSPLAT_ERR_INVALID_ARG for a NULL args or required pointer, N < 1, voxel_size not in
+ * (0, inf), a negative cap_v or a positive one without the buffer of an array that was given; DNSPLAT_ERR_UNSUPPORTED for
+ * N > (2^31 - 1) / 2; DNSPLAT_ERR_WORKSPACE for a short or misaligned scratch.
+ * Out of scope: estimate_normals, remove_radius_outlier, voxel_down_sample_and_trace's matrix form, PLY input and output. */
+#define DNSPLAT_CLOUD_OUTLIER_STATS_BYTES 64
+#define DNSPLAT_VOXEL_STATUS_INTERNAL 1
+#define DNSPLAT_VOXEL_STATUS_NONFINITE 2
+#define DNSPLAT_VOXEL_STATUS_EXTENT 4
+#define DNSPLAT_VOXEL_STATUS_ATTRIBUTE 8
+typedef struct dnsplat_cloud_outlier_args {
+    int32_t N;
+    int32_t nb_neighbors;       /* neighbor_mean; Open3D's callers: 20 */
+    const float *points;        /* neighbor_mean: [N,3] */
+    const void *index;          /* neighbor_mean: dnsplat_knn_build's, over the same points */
+    double std_ratio;           /* stats */
+    void *scratch;
+    size_t scratch_bytes;
+    double *avg;                /* [N]; written by neighbor_mean, read by the others */
+    void *stats;                /* device, DNSPLAT_CLOUD_OUTLIER_STATS_BYTES */
+    int64_t capacity;           /* emit: rows of ind */
+    int64_t *ind;               /* emit: [capacity] */
+} dnsplat_cloud_outlier_args;
+typedef struct dnsplat_voxel_args {
+    int32_t N;
+    const float *points;        /* [N,3] */
+    const float *normals;       /* [N,3] or NULL */
+    const float *colors;        /* [N,3] or NULL */
+    double voxel_size;
+    void *scratch;
+    size_t scratch_bytes;
+    int64_t *counts;            /* device int64 [2]: V, status */
+    int32_t *voxel_of;          /* [N] */
+    int64_t cap_v;              /* emit: rows of the outputs */
+    double *out_points;         /* emit: [cap_v,3] */
+    double *out_normals;        /* emit: [cap_v,3] with normals */
+    double *out_colors;         /* emit: [cap_v,3] with colors */
+    int32_t *out_counts;        /* emit: [cap_v] or NULL */
+} dnsplat_voxel_args;
+size_t dnsplat_cloud_outlier_scratch_bytes(int32_t N);   /* 0 for an invalid size */
+int dnsplat_cloud_neighbor_mean(const dnsplat_cloud_outlier_args *args, dnsplat_stream_t stream);
+int dnsplat_cloud_outlier_stats(const dnsplat_cloud_outlier_args *args, dnsplat_stream_t stream);
+int dnsplat_cloud_outlier_count(const dnsplat_cloud_outlier_args *args, dnsplat_stream_t stream);
+int dnsplat_cloud_outlier_emit(const dnsplat_cloud_outlier_args *args, dnsplat_stream_t stream);
+size_t dnsplat_voxel_scratch_bytes(int32_t N, int32_t n_attributes);   /* 0 for an invalid size */
+int dnsplat_voxel_count(const dnsplat_voxel_args *args, dnsplat_stream_t stream);
+int dnsplat_voxel_emit(const dnsplat_voxel_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
