@@ -296,6 +296,15 @@ class VoxelArgs(ctypes.Structure):
     ]
 
 
+class IcpArgs(ctypes.Structure):
+    _fields_ = [
+        ("M", c_int64), ("source", c_void_p), ("N", c_int32), ("target", c_void_p), ("index", c_void_p),
+        ("max_dist", ctypes.c_double), ("relative_fitness", ctypes.c_double), ("relative_rmse", ctypes.c_double),
+        ("max_iteration", c_int32), ("state", c_void_p), ("trace", c_void_p), ("idx", c_void_p), ("dist2", c_void_p),
+        ("scratch", c_void_p), ("scratch_bytes", c_size_t),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -341,6 +350,9 @@ EXPORTS = [
     # likewise: the fused path's tile lists per cell of several tiles
     "dnsplat_bin_prepare_cells", "dnsplat_bin_emit_sort_cells", "dnsplat_raster_fwd_cells", "dnsplat_raster_bwd_cells",
     "dnsplat_det_reduce_planes",
+    # likewise: the mesh alignment (point-to-point ICP), the rigid transform of points, the points of an index
+    "dnsplat_icp_scratch_bytes", "dnsplat_icp_begin", "dnsplat_icp_iterate", "dnsplat_icp_run", "dnsplat_transform_points",
+    "dnsplat_knn_points",
 ]
 
 _lib = None
@@ -483,6 +495,13 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_voxel_scratch_bytes.argtypes = [c_int32, c_int32]
         L.dnsplat_voxel_count.argtypes = [ctypes.POINTER(VoxelArgs), c_void_p]
         L.dnsplat_voxel_emit.argtypes = [ctypes.POINTER(VoxelArgs), c_void_p]
+        L.dnsplat_icp_scratch_bytes.restype = c_size_t
+        L.dnsplat_icp_scratch_bytes.argtypes = [c_int64]
+        L.dnsplat_icp_begin.argtypes = [ctypes.POINTER(IcpArgs), c_void_p, c_void_p]
+        L.dnsplat_icp_iterate.argtypes = [ctypes.POINTER(IcpArgs), c_void_p]
+        L.dnsplat_icp_run.argtypes = [ctypes.POINTER(IcpArgs), c_void_p, c_void_p]
+        L.dnsplat_transform_points.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]
+        L.dnsplat_knn_points.argtypes = [c_int32, c_void_p, c_void_p, c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
@@ -490,7 +509,7 @@ def lib() -> ctypes.CDLL:
                             "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
                             "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes",
                             "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_cloud_outlier_scratch_bytes",
-                            "dnsplat_voxel_scratch_bytes"):
+                            "dnsplat_voxel_scratch_bytes", "dnsplat_icp_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, VoxelArgs, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, IcpArgs, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, VoxelArgs, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -586,6 +586,17 @@ def _voxel_args(points, normals, colors, voxel_size, scratch, counts, voxel_of, 
     a.counts, a.voxel_of = _ptr(counts), _ptr(voxel_of)
     a.cap_v = 0 if out_points is None else out_points.shape[0]
     a.out_points, a.out_normals, a.out_colors, a.out_counts = _ptr(out_points), _ptr(out_normals), _ptr(out_colors), _ptr(out_counts)
+    return a
+
+
+def _icp_args(source, target, index, max_dist, relative_fitness, relative_rmse, max_iteration, state, scratch, trace=None, idx=None,
+              dist2=None):
+    a = IcpArgs()
+    a.M, a.source = source.shape[0], _ptr(source)
+    a.N, a.target, a.index = target.shape[0], _ptr(target), _ptr(index)
+    a.max_dist, a.relative_fitness, a.relative_rmse, a.max_iteration = max_dist, relative_fitness, relative_rmse, max_iteration
+    a.state, a.trace, a.idx, a.dist2 = _ptr(state), _ptr(trace), _ptr(idx), _ptr(dist2)
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
     return a
 
 

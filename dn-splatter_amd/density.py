@@ -59,10 +59,21 @@ class KnnIndex:
         L = _lib.lib()
         self.buffer = torch.empty(L.dnsplat_knn_index_bytes(self.N) // 8, dtype=torch.int64, device=points.device)
         _lib.run("dnsplat_knn_build", L.dnsplat_knn_build, self.N, _ptr(points), _ptr(self.buffer), _stream())
+        self._points = None
 
     @property
     def device(self):
         return self.buffer.device
+
+    def points(self) -> Tensor:
+        """float32 [N,3]: the points the index was built over, in their own order and bit for bit, recovered from the sorted copy the
+        buffer holds (``dnsplat_knn_points``); kept after the first call.  The mesh alignment reads its targets from it."""
+        if self._points is None:
+            out = torch.empty(self.N, 3, dtype=torch.float32, device=self.device)
+            L = _lib.lib()
+            _lib.run("dnsplat_knn_points", L.dnsplat_knn_points, self.N, _ptr(self.buffer), _ptr(out), _stream())
+            self._points = out
+        return self._points
 
     def query(self, queries: Tensor, k: int, skip: int = 0, return_d2: bool = False):
         """int32 [M,k]: ranks ``skip .. skip + k - 1`` by (d², index), d² in float64; with ``return_d2`` also d² as float32 [M,k]."""

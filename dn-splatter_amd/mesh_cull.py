@@ -11,12 +11,13 @@ numpy loop over the poses and cuts with trimesh, this module keeps mesh, maps an
   * ``vertex_visibility``: ``get_grid_culling_pattern``, ``dnsplat_mesh_visibility``; the votes accumulate, so camera batches chain;
   * ``cut_mesh``: the triangle rule and ``remove_unreferenced_vertices``, ``dnsplat_mesh_cut_count`` / ``dnsplat_mesh_cut_emit``;
   * ``cull_mesh``: the three in batches of ``camera_batch`` cameras through one reused depth buffer; the host reads (V', T') once;
-  * ``culled_mesh_metrics``: ``main()`` — cull both meshes, then ``geometry.mesh_metrics``.
+  * ``culled_mesh_metrics``: ``main()`` — with ``align`` the ICP alignment of ``icp`` first, then cull both meshes, then
+    ``geometry.mesh_metrics``.
 
 Poses are camera-to-world [C,4,4] in the OpenGL convention, as the reference hands them to pyrender and to ``cull_from_one_pose``;
 ``torch_mesh_cull.opencv_w2c`` turns them into the OpenCV ``[R | t]`` rows the kernels take.  Vertices are float32 (float64 is rounded
 once, as in ``geometry``).  Out of scope: ``subdivide_to_size`` (pass the mesh to be voted on: a marching-cubes mesh at a voxel edge
-at or under ``max_edge`` needs none), ICP alignment, ``voxel_down_sample``, PLY / JSON input and output, the CLIs, the 2-D contour cut
+at or under ``max_edge`` needs none), ``voxel_down_sample``, PLY / JSON input and output, the CLIs, the 2-D contour cut
 of the MuSHRoom variant.  CPU tensors are refused; there is no CPU fallback."""
 from __future__ import annotations
 
@@ -190,9 +191,16 @@ def cull_mesh(mesh, poses, K, height: int, width: int, depth_gt=None, remove_mis
 
 @torch.no_grad()
 def culled_mesh_metrics(pred, target, poses, K, height: int, width: int, depth_gt=None, threshold: float = 0.05, seed: int = 0,
-                        samples_per_area: float = 1e4, count: Optional[Tuple[int, int]] = None, **kw) -> Dict[str, Tensor]:
-    """``main()`` of eval_mesh_vis_cull.py:439-464 behind its loading and alignment: both meshes through ``cull_mesh`` with the same poses,
-    intrinsics and sensor depth (``**kw``: its other arguments), then ``geometry.mesh_metrics`` on the two culled meshes."""
+                        samples_per_area: float = 1e4, count: Optional[Tuple[int, int]] = None, align: bool = False,
+                        align_threshold: float = 0.1, **kw) -> Dict[str, Tensor]:
+    """``main()`` of eval_mesh_vis_cull.py:427-464 behind its loading: with ``align`` (:427-431) the prediction is first moved by
+    ``icp.get_align_transformation(pred, target, align_threshold)``; then both meshes go through ``cull_mesh`` with the same poses,
+    intrinsics and sensor depth (``**kw``: its other arguments), then ``geometry.mesh_metrics`` on the two culled meshes.  Without
+    ``align``, the default, nothing is moved."""
+    if align:
+        from .icp import get_align_transformation, transform_mesh
+
+        pred = transform_mesh(pred, get_align_transformation(pred, target, align_threshold))
     pred = cull_mesh(pred, poses, K, height, width, depth_gt, **kw)
     target = cull_mesh(target, poses, K, height, width, depth_gt, **kw)
     return mesh_metrics(pred, target, threshold=threshold, seed=seed, samples_per_area=samples_per_area, count=count)
