@@ -545,14 +545,26 @@ def half_recipe(n, stop, cap=False):
     raise ValueError(stop)
 
 
-def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=False, seed=0, pad_to=None):
+# ``edge_frame(cell=)``: length of a run of one tile inside its cell's list, by cell index, in pairs of depth slots — a tile's own order
+# has two slots per case entry, the even one for the entry and the odd one for the culled entry ``interleave`` puts in front of every
+# second case entry.  So a run is this many case entries, plus half as many culled ones with ``interleave``.  Long runs leave whole
+# 64-entry batches of a cell's list to ONE tile (all-foreign batches for the others), single entries spread a half tile's bucket over
+# many sparse batches
+EDGE_CELL_RUNS = (128, 1, 40)
+
+
+def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=False, seed=0, pad_to=None, cell=None):
     """Raster-level scene (the inputs of rasterize_to_pixels, CPU tensors) from ``cases`` = [(tile, half, n, stop)], one case per tile.
     Ids: the case entries first (in case order, then list order), then the culled entries ``interleave`` puts in front of every
     second case entry, then the padding; ``pad_to`` appends invisible splats (radius 0) up to that many records.
     ``phase``: the list of case k starts at range_start mod 64 = EDGE_OFFSETS[(k + phase) % 3] (padding entries at the end of the
     tile in front of it, which holds no case).  ``end_align``: the last tile of the frame holds a case, and its list ends on a
     multiple of 64.  Depths are distinct integers in recipe order.  Channels: ``colors8`` / ``background8``, 8 of them in [0.1, 0.9]
-    (a D-channel render takes the first D)."""
+    (a D-channel render takes the first D).
+    ``cell`` = (cw, ch) tiles: the depths of the tiles of one list cell of that shape interleave — runs of EDGE_CELL_RUNS case entries
+    (with the culled entries ``interleave`` puts between them) of each tile in turn — where without it they are assigned tile by
+    tile.  Within a tile the order stays the recipe's, so a tile's own entries, the list lengths and every per-tile regime are what they are without it; the CELL's list, which is what the kernels walk
+    when the lists are kept per cell, is then mostly someone else's to each of its half tiles."""
     tw, th = (W + 15) // 16, (H + 15) // 16
     T = tw * th
     cases = sorted(cases)
@@ -562,6 +574,20 @@ def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=F
     g = torch.Generator().manual_seed(seed)
     stride = 2 * max([c[2] for c in cases] + [1]) + 2 * 64 + 8
     assert (T + 1) * stride < 2 ** 24, "depths must stay exact in float32"
+    if cell is not None:
+        cw, ch = cell
+        lw, n_cells, K = -(-tw // cw), (-(-tw // cw)) * (-(-th // ch)), cw * ch
+        span = K * (stride + 2 * max(EDGE_CELL_RUNS))
+        assert (n_cells + 1) * span < 2 ** 24, "depths must stay exact in float32"
+
+    def dep(t, local):
+        """the depth of the entry at position ``local`` (< stride) of tile t's own order"""
+        if cell is None:
+            return 1.0 + t * stride + local
+        c, r = (t // tw // ch) * lw + t % tw // cw, (t // tw % ch) * cw + t % tw % cw
+        G = 2 * EDGE_CELL_RUNS[c % len(EDGE_CELL_RUNS)]
+        return 1.0 + c * span + (local // G) * K * G + r * G + local % G
+
     rows = []              # (x, y, conic a, b, c, opacity, radius, depth, kind) kind: 0 case, 1 interleaved culled, 2 padding
     a_pt = 1.0 / EDGE_SIGMA ** 2
     for t, h, n, stop in cases:
@@ -570,12 +596,12 @@ def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=F
         for i, (p, o, centred) in enumerate(half_recipe(n, stop, cap)):
             dx, dy = (CAP_OFFSET, CAP_OFFSET) if centred else (EDGE_JITTER * float(jit[i, 0]), EDGE_JITTER * float(jit[i, 1]))
             rows.append((x0 + p % 16 + 0.5 + dx, y0 + p // 16 + 0.5 + dy, a_pt, 0.0 if centred else 0.3 * float(jit[i, 2]), a_pt, o, 1,
-                         1.0 + t * stride + 2 * i + 2, 0))
+                         dep(t, 2 * i + 2), 0))
     if interleave:
         for t, h, n, stop in cases:
             x0, y0 = 16 * (t % tw), 16 * (t // tw)
             for i in range(0, n, 2):
-                rows.append((x0 + 8.0, y0 + 8.0, 4.0, 0.0, 4.0, CULL_OPACITY, 1, 1.0 + t * stride + 2 * i + 1, 1))
+                rows.append((x0 + 8.0, y0 + 8.0, 4.0, 0.0, 4.0, CULL_OPACITY, 1, dep(t, 2 * i + 1), 1))
 
     def boxes(x, y, r):
         """gsplat's tile box (A.3) of centres x, y and radii r, clipped to the grid"""
@@ -607,7 +633,7 @@ def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=F
     for t in range(T):
         x0, y0 = 16 * (t % tw), 16 * (t // tw)
         for j in range(fill[t]):
-            rows.append((x0 + 8.0, y0 + 8.0, 4.0, 0.0, 4.0, CULL_OPACITY, 1, 1.0 + t * stride + stride - 72 + j, 2))
+            rows.append((x0 + 8.0, y0 + 8.0, 4.0, 0.0, 4.0, CULL_OPACITY, 1, dep(t, stride - 72 + j), 2))
     R = torch.tensor([r[:6] for r in rows], dtype=torch.float64).reshape(-1, 6)
     radii = torch.tensor([r[6] for r in rows], dtype=torch.int32)
     depths = torch.tensor([r[7] for r in rows], dtype=torch.float32)
@@ -628,7 +654,36 @@ def edge_frame(cases, W, H, *, interleave=False, phase=0, end_align=False, cap=F
     bg = 0.1 + 0.8 * torch.rand(8, generator=gc)
     return dict(W=W, H=H, N=N, xys=xys, conics=conics, opacities=opac, colors8=cols, background8=bg, radii=radii, depths=depths,
                 tiles=tiles, kind=kind, n_case=int((kind == 0).sum()), cases=cases, target=target, fill=fill, tw=tw, th=th, phase=phase,
-                interleave=interleave, cap=cap)
+                interleave=interleave, cap=cap, cell=cell)
+
+
+def edge_tile_boxes(s):
+    """gsplat's tile boxes (A.3) of an edge frame as the binning takes them: int32 [N, 2] = (first tile id, w | h << 16), 0 | 0 for the
+    invisible records."""
+    x, y, r = s["xys"][:, 0], s["xys"][:, 1], s["radii"].float()
+    tw, th = s["tw"], s["th"]
+    bx0 = torch.clamp(torch.floor((x - r) / 16), 0, tw).long()
+    bx1 = torch.clamp(torch.ceil((x + r) / 16), 0, tw).long()
+    by0 = torch.clamp(torch.floor((y - r) / 16), 0, th).long()
+    by1 = torch.clamp(torch.ceil((y + r) / 16), 0, th).long()
+    vis = s["radii"] > 0
+    assert torch.equal(torch.where(vis, (bx1 - bx0) * (by1 - by0), torch.zeros_like(bx0)).to(torch.int32), s["tiles"])
+    z = torch.zeros_like(bx0)
+    return torch.stack([torch.where(vis, by0 * tw + bx0, z), torch.where(vis, (bx1 - bx0) | ((by1 - by0) << 16), z)], 1).to(torch.int32)
+
+
+def edge_cell_lists(frames, sx, sy):
+    """The lists of a batch of edge frames per cell of 2^sx x 2^sy tiles, from the frames' tile boxes and depths alone (the numpy
+    restatement of _cell_binning_ref.py): (offsets [C * cells + 1] int64, flatten_ids int64 with entry = camera x N + record)."""
+    import numpy as np
+
+    import _cell_binning_ref as ref
+
+    boxes = torch.cat([edge_tile_boxes(s) for s in frames]).numpy()
+    radii = torch.cat([s["radii"] for s in frames]).numpy()
+    depths = torch.cat([s["depths"] for s in frames]).numpy()
+    got = ref.cell_lists(boxes, radii, depths, frames[0]["tw"], frames[0]["th"], len(frames), sx, sy)
+    return torch.from_numpy(got["offsets"].astype(np.int64)), torch.from_numpy(got["flatten_ids"].astype(np.int64))
 
 
 def edge_main_cases():
@@ -674,26 +729,48 @@ def edge_lists(orc, s):
     return orc.isect_offset_encode(ids, s["tw"], s["th"]), fid
 
 
-def edge_model(s, offs, fid):
+def edge_model(s, offs, fid, cells=None):
     """What the compositing kernels do on each half tile of ``s``, recomputed in float64 from the lists (offs, fid): one dict per
     (non-empty tile, half) with rs / re (list range), kept (entries with alpha >= 1/255 at some pixel centre of the half: what the
     rectangle test keeps), contrib (those reaching an in-image pixel), stop {pixel: list index (relative) of the entry that stops it},
     hi (the backward's walk bound, relative; -1: no work), queue (kept entries up to hi), the bucket sequence with keep masks (takes /
     carries _masks: 64-entry batches aligned to the list start) and without (_scan: 64 entries down from hi) and the fold of the last
-    bucket in the default mode.  Asserts that no alpha lies within 30 % of 1/255 and no transmittance within 20 % of 1e-4."""
+    bucket in the default mode.  Asserts that no alpha lies within 30 % of 1/255 and no transmittance within 20 % of 1e-4.
+    ``cells`` = (sx, sy): (offs, fid) are the lists of ONE camera per cell of 2^sx x 2^sy tiles (edge_cell_lists), and every half tile of
+    a cell walks the cell's list: an entry is the half tile's only if its own tile box holds the tile (the kernels' rule,
+    dns_tile_in_box) and the rectangle test keeps it — rs, re, hi, the stops, the queue, the bucket sequences and the fold are then
+    those of the list the kernels really walk (positions in the cell's list), ``list`` is the cell.
+    Beside the counts: kept_ids / contrib_ids (entry ids), stop_ids {pixel: id of the entry that stops it}, batches_masks (64-entry
+    batches taken per bucket with keep masks), foreign_gap (a batch none of whose entries has the tile in its box lies between two
+    batches the half tile queues entries of) and stop_ends_batch (a stopping entry is the last of a batch of the list)."""
     W, H, tw, th = s["W"], s["H"], s["tw"], s["th"]
     T = tw * th
     offs = offs.reshape(-1).long()
     xy, cn, op = s["xys"].double(), s["conics"].double(), s["opacities"].double()
     amin, tmin = 1.0 / 255.0, 1e-4
     out = []
-    for t in range(T):
-        rs = int(offs[t])
-        re = int(offs[t + 1]) if t + 1 < T else fid.numel()
+    if cells is None:
+        walks = [(t, t, None) for t in range(T)]
+    else:
+        sx, sy = cells
+        lw = (tw + (1 << sx) - 1) >> sx
+        tb = edge_tile_boxes(s).long()
+        bx0, by0, bw, bh = tb[:, 0] % tw, tb[:, 0] // tw, tb[:, 1] & 0xffff, tb[:, 1] >> 16
+        walks = [(t, (t // tw >> sy) * lw + (t % tw >> sx), t) for t in range(T)]
+    for t, l, boxed in walks:
+        rs = int(offs[l])
+        re = int(offs[l + 1]) if l + 1 < offs.numel() else fid.numel()
         if re <= rs:
             continue
         ids = fid[rs:re].long()
         L = re - rs
+        if boxed is None:
+            own = torch.ones(L, dtype=torch.bool)
+        else:
+            tx, ty = t % tw, t // tw
+            own = (bx0[ids] <= tx) & (tx < bx0[ids] + bw[ids]) & (by0[ids] <= ty) & (ty < by0[ids] + bh[ids])
+            if not bool(own.any()):
+                continue                                                  # the tile's own list is empty: as without cells
         for h in (0, 1):
             px = (16 * (t % tw) + torch.arange(16, dtype=torch.float64) + 0.5).repeat(8)
             py = (16 * (t // tw) + 8 * h + torch.arange(8, dtype=torch.float64) + 0.5).repeat_interleave(16)
@@ -703,7 +780,7 @@ def edge_model(s, offs, fid):
             sig = 0.5 * (cn[ids, 0:1] * dx * dx + cn[ids, 2:3] * dy * dy) + cn[ids, 1:2] * dx * dy
             al = torch.clamp(op[ids, None] * torch.exp(-sig), max=0.999)
             assert not bool(((al > 0.7 * amin) & (al < 1.3 * amin)).any()), f"tile {t} half {h}: an alpha within 30 % of 1/255"
-            valid = (sig >= 0) & (al >= amin)
+            valid = (sig >= 0) & (al >= amin) & own[:, None]
             kept = valid.any(1)
             vin = valid & inimg[None, :]
             lg = torch.where(vin, torch.log1p(-al), torch.zeros_like(al))
@@ -727,11 +804,12 @@ def edge_model(s, offs, fid):
             q = kept & (torch.arange(L) <= hi - rs) if hi >= rs else torch.zeros(L, dtype=torch.bool)
 
             def buckets(masks):
-                qn, takes, carries = 0, [], []
+                qn, takes, carries, pulled = 0, [], [], []
                 if hi < rs:
-                    return takes, carries
+                    return takes, carries, pulled
                 batch, cursor = (hi - rs) >> 6, hi
                 while True:
+                    n_b = 0
                     while qn < 128 and (batch >= 0 if masks else cursor >= rs):
                         if masks:
                             qn += int(q[64 * batch:64 * batch + 64].sum())
@@ -739,19 +817,30 @@ def edge_model(s, offs, fid):
                         else:
                             qn += int(q[max(rs, cursor - 63) - rs:cursor - rs + 1].sum())
                             cursor -= 64
+                        n_b += 1
                     take = min(qn, 128)
                     qn -= take
                     takes.append(take)
                     carries.append(qn)
+                    pulled.append(n_b)
                     if take == 0:
-                        return takes, carries
-            tm, cm = buckets(True)
-            ts, cs = buckets(False)
+                        return takes, carries, pulled
+            tm, cm, bm = buckets(True)
+            ts, cs, _bs = buckets(False)
             last = ([x for x in tm if x > 0] or [0])[-1]
+            nb = (L + 63) // 64
+            pad = torch.zeros(nb * 64 - L, dtype=torch.bool)
+            own_b = torch.cat([own, pad]).reshape(nb, 64).any(1)
+            q_b = torch.cat([q, pad]).reshape(nb, 64).any(1)
+            with_q = torch.nonzero(q_b).reshape(-1)
+            gap = bool(with_q.numel() >= 2 and (~own_b[int(with_q[0]):int(with_q[-1]) + 1]).any())
             out.append(dict(tile=t, half=h, rs=rs, re=re, L=L, kept=int(kept.sum()), contrib=int(vin.any(1).sum()), stop=stop,
                             hi=(hi - rs) if hi >= rs else -1, queue=int(q.sum()), takes_masks=tm, carries_masks=cm, takes_scan=ts,
                             carries_scan=cs, fold=4 if 0 < last <= 32 else 2 if 0 < last <= 64 else 1, n_stopped=len(stop),
-                            n_blending=int((bin_final >= 0).sum()), kept_above_hi=int(kept[max(hi - rs + 1, 0):].sum())))
+                            n_blending=int((bin_final >= 0).sum()), kept_above_hi=int(kept[max(hi - rs + 1, 0):].sum()),
+                            list=l, kept_ids=ids[kept].tolist(), contrib_ids=ids[vin.any(1)].tolist(),
+                            stop_ids={p: int(ids[st]) for p, st in stop.items()}, batches_masks=bm, foreign_gap=gap,
+                            stop_ends_batch=any(st % 64 == 63 for st in stop.values())))
     return out
 
 
@@ -763,7 +852,9 @@ def regime_line(r, what=""):
             f"kept {r['kept']} (in the image {r['contrib']}), {r['n_stopped']} of {r['n_blending']} blending pixels stop"
             f"{' at ' + str(st[:4]) if st else ''}, hi {r['hi']}, queue {r['queue']} (+{r['kept_above_hi']} kept above hi), buckets "
             f"{tm if len(tm) <= 5 else tm[:2] + ['...'] + tm[-2:]}, fold {r['fold']}, carried max {max(r['carries_masks'] or [0])} "
-            f"(masks) / {max(r['carries_scan'] or [0])} (scan)")
+            f"(masks) / {max(r['carries_scan'] or [0])} (scan)"
+            + (f"; walks the list of cell {r['list']}: a bucket takes up to {max(r['batches_masks'] or [0])} batches, "
+               f"{'an' if r['foreign_gap'] else 'no'} all-foreign batch inside the walk" if r.get("list", r["tile"]) != r["tile"] else ""))
 
 
 HULL_KEYS = ("means2d", "absgrad", "conics", "colors", "opacities")

@@ -4,8 +4,8 @@ indices, the backward's bound `hi`, bucket sizes, folds and queue carries — so
 import pytest
 import torch
 
-from _scenes import (EDGE_BOUNDARY_STOPS, EDGE_COUNTS, EDGE_OFFSETS, EDGE_SMALL, allstop_groups, edge_cameras, edge_frame, edge_lists,
-                     edge_main_cases, edge_model)
+from _scenes import (EDGE_BOUNDARY_STOPS, EDGE_COUNTS, EDGE_OFFSETS, EDGE_SMALL, allstop_groups, edge_cameras, edge_cell_lists, edge_frame,
+                     edge_lists, edge_main_cases, edge_model)
 
 
 def _by_half(model):
@@ -131,3 +131,73 @@ def test_camera_batch_frames_end_on_a_batch_boundary(orc):
         last = int(offs.reshape(-1)[-1])
         assert last < fid.numel(), "the last tile's list is not empty"
         _check_cases(s, offs, fid, edge_model(s, offs, fid))
+
+
+# ---- the same frames when the lists are kept per cell of several tiles (tests/test_gpu_raster_cell_edges.py) ---------------------------
+
+
+def _cell_models(orc, frames, sx, sy):
+    """Per camera: (per-tile model, cell model) by (tile, half); asserts that every half tile keeps, blends and stops on the same
+    entries whether it walks its tile's list or its cell's."""
+    coffs, cfid = edge_cell_lists(frames, sx, sy)
+    n_cells = (coffs.numel() - 1) // len(frames)
+    out = []
+    for c, s in enumerate(frames):
+        offs, fid = edge_lists(orc, s)
+        per_tile = _by_half(edge_model(s, offs, fid))
+        per_cell = _by_half(edge_model(s, coffs[c * n_cells:(c + 1) * n_cells + 1], cfid - c * s["N"], cells=(sx, sy)))
+        assert set(per_tile) == set(per_cell)
+        for key, r in per_tile.items():
+            q = per_cell[key]
+            assert q["kept_ids"] == r["kept_ids"] and q["contrib_ids"] == r["contrib_ids"] and q["stop_ids"] == r["stop_ids"], key
+            assert (q["kept"], q["contrib"], q["n_stopped"], q["n_blending"]) == (r["kept"], r["contrib"], r["n_stopped"], r["n_blending"])
+            assert q["L"] >= r["L"] and q["list"] == (key[0] // s["tw"] >> sy) * ((s["tw"] + (1 << sx) - 1) >> sx) + (key[0] % s["tw"] >> sx)
+        out.append((per_tile, per_cell))
+    return out
+
+
+def _assert_cell_regimes(models, what):
+    """What sets the CELLS kernels apart from their parents, each reached by at least one half tile."""
+    rs = [r for _t, per_cell in models for r in per_cell.values()]
+    live = [r for r in rs if r["queue"] > 0]
+    print(f"[raster] {what}: {len(live)} half tiles with work; all-foreign batch inside the walk: {sum(r['foreign_gap'] for r in live)}; "
+          f"most batches per full bucket: {max([b for r in live for tk, b in zip(r['takes_masks'], r['batches_masks']) if tk == 128] or [0])}")
+    assert any(r["foreign_gap"] for r in live), what + ": no half tile has an all-foreign batch between two batches it keeps entries of"
+    assert any(tk == 128 and b > 4 for r in live for tk, b in zip(r["takes_masks"], r["batches_masks"])), \
+        what + ": no 128-entry bucket is filled from more than four batches"
+    assert {r["fold"] for r in live} == {1, 2, 4}, what
+    assert any(max(r["carries_masks"] or [0]) > 0 for r in rs) and any(max(r["carries_scan"] or [0]) > 0 for r in rs), what
+    assert any(r["kept_above_hi"] > 0 for r in rs), what
+    assert any(r["stop_ends_batch"] for r in rs), what + ": no stop whose entry is the last of a batch of the cell list"
+
+
+@pytest.mark.parametrize("cw,ch", [(2, 2), (4, 2)])
+def test_cell_interleaved_main_frame_reaches_the_cell_regimes(orc, cw, ch):
+    sx, sy = cw.bit_length() - 1, ch.bit_length() - 1
+    plain = edge_frame(edge_main_cases(), 256, 256, interleave=True)
+    s = edge_frame(edge_main_cases(), 256, 256, interleave=True, cell=(cw, ch))
+    # the same records but for the depths, every list as long as it was, every tile's own entries in the recipe's order
+    for k in ("xys", "conics", "opacities", "radii", "tiles", "kind", "colors8"):
+        assert torch.equal(s[k], plain[k]), k
+    assert s["fill"] == plain["fill"] and not torch.equal(s["depths"], plain["depths"])
+    assert bool((s["depths"] == s["depths"].double().float()).all()) and float(s["depths"].max()) < 2 ** 24
+    assert s["depths"].unique().numel() == s["N"]
+    offs, fid = edge_lists(orc, s)
+    offs0, fid0 = edge_lists(orc, plain)
+    assert torch.equal(offs, offs0)
+    m0 = _by_half(edge_model(plain, offs0, fid0))
+    (per_tile, per_cell), = _cell_models(orc, [s], sx, sy)
+    for key, r in m0.items():
+        assert per_tile[key]["kept_ids"] == r["kept_ids"] and per_tile[key]["stop_ids"] == r["stop_ids"], key
+    _assert_cell_regimes([(per_tile, per_cell)], f"main frame interleaved over {cw}x{ch} cells")
+    # the frame as it was, under the same cells: the control — a half tile's entries are one contiguous run of its cell's list
+    (_pt, pc0), = _cell_models(orc, [plain], sx, sy)
+    assert not any(r["foreign_gap"] for r in pc0.values())
+
+
+def test_cell_interleaved_camera_batch(orc):
+    frames = edge_cameras(cell=(2, 2))
+    assert len({s["N"] for s in frames}) == 1
+    models = _cell_models(orc, frames, 1, 1)
+    _assert_cell_regimes(models, "three cameras interleaved over 2x2 cells")
+    assert any(r["rs"] > 0 and r["tile"] < 16 for r in models[2][1].values()), "the last camera's lists start inside the batch"

@@ -186,6 +186,18 @@ def _fused_tight_vs_gsplat(dns, gp, cam, what):
             torch.cuda.synchronize()
             assert bool(m.last_info.get("tight_tiles")) == tight
             figs[tight] = _regime(m.last_info, f"{what}, fused pass, {'tight' if tight else 'gsplat'} boxes")
+            if tight:
+                # every frame this helper sees has 1024 tiles or more: the tight run keeps its lists per 2x2 cell, and the route of ITS
+                # tile sort is picked from the cell grid
+                info = m.last_info
+                cw, ch = info["cell_shape"]
+                lw, lh = -(-int(info["tile_width"]) // cw), -(-int(info["tile_height"]) // ch)
+                bits = _tile_bits(lw * lh)
+                print(f"[binning] {what}, fused pass, tight boxes: lists per {cw}x{ch} cell: {lw * lh} cells ({lw} x {lh}), {bits} bits -> "
+                      f"{(bits + 7) // 8} passes on uint{16 if lw * lh <= 0x10000 else 32} keys, row division "
+                      f"{'fp32 reciprocal' if lw <= 256 and lw * lh <= 65536 else 'integer'}, {int(info['n_cell_pairs'])} cell pairs for "
+                      f"{int(info['n_isects'])} tile pairs")
+                assert (cw, ch) == (2, 2) and 0 < int(info["n_cell_pairs"]) < int(info["n_isects"]), "the tight run did not take list cells"
             assert_binning_properties(m.last_info)
             outs[tight] = {k: out[k].detach().clone() for k in OUT_KEYS}
             del m, out

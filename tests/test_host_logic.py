@@ -452,21 +452,37 @@ def test_capacity_guesses_are_carried_over_a_refinement(dns):
     from dn_splatter_amd import _ops, densify
 
     dev = torch.device("cpu")
-    hints = _ops.BUFFERS.capacity_hint
-    saved = dict(hints)
+    hints, cell_hints = _ops.BUFFERS.capacity_hint, _ops.BUFFERS.cell_hint
+    saved, saved_cells = dict(hints), dict(cell_hints)
     try:
         hints.clear()
+        cell_hints.clear()
         hints[(dev, 1000, 640, 480)] = 50_000
         hints[(dev, 1000, 320, 240)] = 20_000
         hints[(dev, 777, 640, 480)] = 9_000                       # another Gaussian set: untouched
+        cell_hints[(dev, 1000, 640, 480, 1, 1)] = 30_000          # the (cell, Gaussian) pairs of the same frames under 2x2 cells
+        cell_hints[(dev, 777, 640, 480, 1, 1)] = 5_000
         new = {"means": torch.zeros(1500, 3)}
+        # the cell-pair guesses travel with the per-tile ones and are not counted
+        assert _ops.carry_capacity_guesses(dev, 1000, 1000) == 2 and cell_hints[(dev, 1000, 640, 480, 1, 1)] == int(30_000 * 1.1) + 4096
+        hints[(dev, 1000, 640, 480)], hints[(dev, 1000, 320, 240)], cell_hints[(dev, 1000, 640, 480, 1, 1)] = 50_000, 20_000, 30_000
         densify.after_refinement(new, report={"n_before": 1000})
         assert hints[(dev, 1500, 640, 480)] == int(50_000 * 1.5 * 1.1) + 4096 and hints[(dev, 1500, 320, 240)] == int(20_000 * 1.5 * 1.1) + 4096
         assert (dev, 1000, 640, 480) not in hints and hints[(dev, 777, 640, 480)] == 9_000
+        assert cell_hints[(dev, 1500, 640, 480, 1, 1)] == int(30_000 * 1.5 * 1.1) + 4096          # carried under the new N
+        assert (dev, 1000, 640, 480, 1, 1) not in cell_hints and cell_hints[(dev, 777, 640, 480, 1, 1)] == 5_000
         densify.after_refinement({"means": torch.zeros(1500, 3)}, report={"n_before": 1500})     # size unchanged: guesses stay
         assert hints[(dev, 1500, 640, 480)] == int(50_000 * 1.5 * 1.1) + 4096
+        assert cell_hints[(dev, 1500, 640, 480, 1, 1)] == int(30_000 * 1.5 * 1.1) + 4096
+        # fewer Gaussians: never scaled down (x 1.1 and the margin only), and the return value counts the per-tile guesses alone
+        before = cell_hints[(dev, 1500, 640, 480, 1, 1)]
+        assert _ops.carry_capacity_guesses(dev, 1500, 900) == 2
+        assert cell_hints[(dev, 900, 640, 480, 1, 1)] == int(before * 1.1) + 4096 and (dev, 1500, 640, 480, 1, 1) not in cell_hints
+        assert hints[(dev, 900, 640, 480)] == int((int(50_000 * 1.5 * 1.1) + 4096) * 1.1) + 4096
         densify.after_refinement({"means": torch.zeros(900, 3)})                                  # no report: dropped (all of the device)
-        assert not any(k[0] == dev for k in hints)
+        assert not any(k[0] == dev for k in hints) and not any(k[0] == dev for k in cell_hints)
     finally:
         hints.clear()
         hints.update(saved)
+        cell_hints.clear()
+        cell_hints.update(saved_cells)
