@@ -45,6 +45,8 @@ from . import cloud_filter, torch_cloud_filter  # noqa: F401
 from .cloud_filter import remove_statistical_outlier, voxel_down_sample  # noqa: F401
 from . import icp, torch_icp  # noqa: F401
 from .icp import ICPResult, get_align_transformation, registration_icp, transform_mesh, transform_points  # noqa: F401
+from . import subdivide, torch_subdivide  # noqa: F401
+from .subdivide import subdivide_mesh, subdivide_to_size  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -62,5 +64,6 @@ __all__ = [
     "mesh_clusters", "torch_mesh_clusters", "cluster_connected_triangles", "filter_small_clusters",
     "cloud_filter", "torch_cloud_filter", "remove_statistical_outlier", "voxel_down_sample",
     "icp", "torch_icp", "ICPResult", "registration_icp", "get_align_transformation", "transform_points", "transform_mesh",
+    "subdivide", "torch_subdivide", "subdivide_to_size", "subdivide_mesh",
     "build_library", "load_library", "DnsplatError",
 ]

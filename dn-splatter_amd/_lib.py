@@ -305,6 +305,16 @@ class IcpArgs(ctypes.Structure):
     ]
 
 
+class SubdivideArgs(ctypes.Structure):
+    _fields_ = [
+        ("V", c_int32), ("T", c_int32), ("vertices", c_void_p), ("triangles", c_void_p), ("origin", c_void_p),
+        ("max_edge", ctypes.c_double), ("scratch", c_void_p), ("scratch_bytes", c_size_t), ("counts", c_void_p), ("status", c_void_p),
+        ("vertex_base", c_int64), ("cap_v", c_int64), ("cap_t", c_int64), ("cap_long", c_int64), ("cap_mid", c_int64),
+        ("out_vertices", c_void_p), ("out_triangles", c_void_p), ("out_index", c_void_p),
+        ("next_vertices", c_void_p), ("next_triangles", c_void_p), ("next_origin", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -353,6 +363,8 @@ EXPORTS = [
     # likewise: the mesh alignment (point-to-point ICP), the rigid transform of points, the points of an index
     "dnsplat_icp_scratch_bytes", "dnsplat_icp_begin", "dnsplat_icp_iterate", "dnsplat_icp_run", "dnsplat_transform_points",
     "dnsplat_knn_points",
+    # likewise: the subdivision of long triangles in front of the culling
+    "dnsplat_subdivide_scratch_bytes", "dnsplat_subdivide_count", "dnsplat_subdivide_emit",
 ]
 
 _lib = None
@@ -502,6 +514,10 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_icp_run.argtypes = [ctypes.POINTER(IcpArgs), c_void_p, c_void_p]
         L.dnsplat_transform_points.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]
         L.dnsplat_knn_points.argtypes = [c_int32, c_void_p, c_void_p, c_void_p]
+        L.dnsplat_subdivide_scratch_bytes.restype = c_size_t
+        L.dnsplat_subdivide_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_subdivide_count.argtypes = [ctypes.POINTER(SubdivideArgs), c_void_p]
+        L.dnsplat_subdivide_emit.argtypes = [ctypes.POINTER(SubdivideArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
@@ -509,7 +525,7 @@ def lib() -> ctypes.CDLL:
                             "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
                             "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes",
                             "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_cloud_outlier_scratch_bytes",
-                            "dnsplat_voxel_scratch_bytes", "dnsplat_icp_scratch_bytes"):
+                            "dnsplat_voxel_scratch_bytes", "dnsplat_icp_scratch_bytes", "dnsplat_subdivide_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, IcpArgs, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, TsdfArgs, VoxelArgs, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, IcpArgs, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, SubdivideArgs, TsdfArgs, VoxelArgs, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -597,6 +597,24 @@ def _icp_args(source, target, index, max_dist, relative_fitness, relative_rmse, 
     a.max_dist, a.relative_fitness, a.relative_rmse, a.max_iteration = max_dist, relative_fitness, relative_rmse, max_iteration
     a.state, a.trace, a.idx, a.dist2 = _ptr(state), _ptr(trace), _ptr(idx), _ptr(dist2)
     a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    return a
+
+
+def _subdivide_args(vertices, triangles, origin, max_edge, scratch, counts, status, vertex_base=0, out_vertices=None, out_triangles=None,
+                    out_index=None, next_vertices=None, next_triangles=None, next_origin=None):
+    a = SubdivideArgs()
+    a.V, a.T = vertices.shape[0], triangles.shape[0]
+    a.vertices, a.triangles, a.origin = _ptr(vertices), _ptr(triangles), _ptr(origin)
+    a.max_edge = max_edge
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.counts, a.status = _ptr(counts), _ptr(status)
+    a.vertex_base = vertex_base
+    a.cap_v = 0 if out_vertices is None else out_vertices.shape[0]
+    a.cap_t = 0 if out_triangles is None else out_triangles.shape[0]
+    a.cap_long = 0 if next_origin is None else next_origin.shape[0] // 4
+    a.cap_mid = 0 if next_vertices is None else next_vertices.shape[0] - vertices.shape[0]
+    a.out_vertices, a.out_triangles, a.out_index = _ptr(out_vertices), _ptr(out_triangles), _ptr(out_index)
+    a.next_vertices, a.next_triangles, a.next_origin = _ptr(next_vertices), _ptr(next_triangles), _ptr(next_origin)
     return a
 
 

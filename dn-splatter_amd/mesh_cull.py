@@ -16,9 +16,9 @@ numpy loop over the poses and cuts with trimesh, this module keeps mesh, maps an
 
 Poses are camera-to-world [C,4,4] in the OpenGL convention, as the reference hands them to pyrender and to ``cull_from_one_pose``;
 ``torch_mesh_cull.opencv_w2c`` turns them into the OpenCV ``[R | t]`` rows the kernels take.  Vertices are float32 (float64 is rounded
-once, as in ``geometry``).  Out of scope: ``subdivide_to_size`` (pass the mesh to be voted on: a marching-cubes mesh at a voxel edge
-at or under ``max_edge`` needs none), ``voxel_down_sample``, PLY / JSON input and output, the CLIs, the 2-D contour cut
-of the MuSHRoom variant.  CPU tensors are refused; there is no CPU fallback."""
+once, as in ``geometry``).  The reference's first step, ``trimesh.remesh.subdivide_to_size`` (:190-193), is ``subdivide`` and runs
+with ``cull_mesh(..., subdivide=True)``; a marching-cubes mesh at a voxel edge at or under ``max_edge`` needs none, which is the
+default.  Out of scope: ``voxel_down_sample``, PLY / JSON input and output, the CLIs, the 2-D contour cut of the MuSHRoom variant.  CPU tensors are refused; there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes
@@ -158,14 +158,22 @@ def cut_mesh(vertices, triangles, obs: Tensor, invalid: Tensor, obs_threshold: i
 
 @torch.no_grad()
 def cull_mesh(mesh, poses, K, height: int, width: int, depth_gt=None, remove_missing_depth: bool = True, remove_occlusion: bool = True,
-              obs_threshold: int = OBS_THRESHOLD, invalid_share: float = INVALID_SHARE, camera_batch: int = 8) -> Tuple[Tensor, Tensor]:
-    """``cull_mesh`` (:176-266) without its subdivision: ``mesh`` is a (vertices, triangles, ...) tuple — what ``marching_cubes_mesh``
+              obs_threshold: int = OBS_THRESHOLD, invalid_share: float = INVALID_SHARE, camera_batch: int = 8, subdivide: bool = False,
+              max_edge: float = 0.015, max_iter: int = 10) -> Tuple[Tensor, Tensor]:
+    """``cull_mesh`` (:176-266): ``mesh`` is a (vertices, triangles, ...) tuple — what ``marching_cubes_mesh``
     returns.  ``camera_batch`` poses at a time are rendered into one reused depth buffer and voted on before the next batch (a few
     hundred 1080p maps would be gigabytes); the votes are integers, so the result does not depend on the batch size.  ``depth_gt`` is
     [C,H,W] (a tensor on the device or an array), ``None`` implies ``remove_missing_depth=False``.  Returns (vertices float32 [V',3],
-    triangles int32 [T',3]) on the device; the host reads (V', T') once."""
+    triangles int32 [T',3]) on the device; the host reads (V', T') once.  With ``subdivide`` (the reference's ``subdivide=True``,
+    :190-193) the depth maps are still rendered from the GIVEN mesh (:229-235), and the votes and the cut run on
+    ``subdivide.subdivide_mesh(mesh, max_edge, max_iter)``, rounded to float32 once; that adds one host read per round."""
     vertices, triangles = _mesh(mesh, "mesh")
     height, width = _frame(height, width)
+    render_vertices, render_triangles = vertices, triangles
+    if subdivide:
+        from .subdivide import subdivide_mesh
+
+        vertices, triangles = _mesh(subdivide_mesh(mesh, max_edge, max_iter), "mesh")
     dev, V = vertices.device, vertices.shape[0]
     camera_batch = int(camera_batch)
     if camera_batch < 1:
@@ -183,7 +191,7 @@ def cull_mesh(mesh, poses, K, height: int, width: int, depth_gt=None, remove_mis
     buffer = torch.empty(min(camera_batch, C) * height * width, dtype=torch.float32, device=dev) if remove_occlusion else None
     for s in range(0, C, camera_batch):
         batch = P[s:s + camera_batch]
-        rendered = render_mesh_depth(vertices, triangles, batch, K, height, width, out=buffer) if remove_occlusion else None
+        rendered = render_mesh_depth(render_vertices, render_triangles, batch, K, height, width, out=buffer) if remove_occlusion else None
         gt = depth_gt[s:s + batch.shape[0]] if remove_missing_depth else None
         vertex_visibility(vertices, batch, K, height, width, rendered, gt, remove_missing_depth, remove_occlusion, obs, invalid)
     return cut_mesh(vertices, triangles, obs, invalid, obs_threshold, invalid_share)

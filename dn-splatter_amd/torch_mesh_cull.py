@@ -215,10 +215,18 @@ def cut_mesh(vertices: Tensor, triangles: Tensor, obs: Tensor, invalid: Tensor, 
 @torch.no_grad()
 def cull_mesh(mesh, poses, K, height: int, width: int, depth_gt: Optional[Tensor] = None, remove_missing_depth: bool = True,
               remove_occlusion: bool = True, obs_threshold: int = OBS_THRESHOLD, invalid_share: float = INVALID_SHARE,
-              camera_batch: int = 8) -> Tuple[Tensor, Tensor]:
-    """``cull_mesh`` without its subdivision: render, vote over the poses in batches of ``camera_batch``, cut.  ``mesh`` is a
-    (vertices float32 [V,3], triangles int [T,3]) pair; ``depth_gt=None`` implies ``remove_missing_depth=False``."""
+              camera_batch: int = 8, subdivide: bool = False, max_edge: float = 0.015, max_iter: int = 10) -> Tuple[Tensor, Tensor]:
+    """``cull_mesh``: render, vote over the poses in batches of ``camera_batch``, cut.  ``mesh`` is a
+    (vertices float32 [V,3], triangles int [T,3]) pair; ``depth_gt=None`` implies ``remove_missing_depth=False``.  With ``subdivide``
+    the render is of the given mesh, and the votes and the cut are on ``torch_subdivide.subdivide_mesh(mesh, max_edge, max_iter)``,
+    rounded to float32 once."""
     vertices, triangles = mesh[0].to(torch.float32), mesh[1]
+    render_vertices, render_triangles = vertices, triangles
+    if subdivide:
+        from .torch_subdivide import subdivide_mesh
+
+        fine_v, fine_t = subdivide_mesh((mesh[0], mesh[1]), max_edge, max_iter)
+        vertices, triangles = fine_v.to(torch.float32).to(mesh[0].device), fine_t.to(mesh[1].device)
     if depth_gt is None:
         remove_missing_depth = False
     w2c_count = opencv_w2c(poses).shape[0]
@@ -226,7 +234,7 @@ def cull_mesh(mesh, poses, K, height: int, width: int, depth_gt: Optional[Tensor
     obs = invalid = None
     for s in range(0, w2c_count, max(int(camera_batch), 1)):
         batch = P[s:s + max(int(camera_batch), 1)]
-        rendered = render_mesh_depth(vertices, triangles, batch, K, height, width) if remove_occlusion else None
+        rendered = render_mesh_depth(render_vertices, render_triangles, batch, K, height, width) if remove_occlusion else None
         gt = depth_gt[s:s + batch.shape[0]] if remove_missing_depth else None
         obs, invalid = vertex_visibility(vertices, batch, K, height, width, rendered, gt, remove_missing_depth, remove_occlusion,
                                          obs, invalid)
