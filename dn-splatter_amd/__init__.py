@@ -47,6 +47,8 @@ from . import icp, torch_icp  # noqa: F401
 from .icp import ICPResult, get_align_transformation, registration_icp, transform_mesh, transform_points  # noqa: F401
 from . import subdivide, torch_subdivide  # noqa: F401
 from .subdivide import subdivide_mesh, subdivide_to_size  # noqa: F401
+from . import normals, torch_normals  # noqa: F401
+from .normals import depth_normals, estimate_normals, normal_consistency_mask, points3D_normals  # noqa: F401
 
 __all__ = [
     "rasterization", "rasterize_gaussians", "quat_to_rotmat", "num_sh_bases", "render_dn",
@@ -65,5 +67,6 @@ __all__ = [
     "cloud_filter", "torch_cloud_filter", "remove_statistical_outlier", "voxel_down_sample",
     "icp", "torch_icp", "ICPResult", "registration_icp", "get_align_transformation", "transform_points", "transform_mesh",
     "subdivide", "torch_subdivide", "subdivide_to_size", "subdivide_mesh",
+    "normals", "torch_normals", "estimate_normals", "points3D_normals", "depth_normals", "normal_consistency_mask",
     "build_library", "load_library", "DnsplatError",
 ]

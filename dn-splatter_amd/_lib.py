@@ -315,6 +315,14 @@ class SubdivideArgs(ctypes.Structure):
     ]
 
 
+class CloudNormalsArgs(ctypes.Structure):
+    _fields_ = [
+        ("N", c_int32), ("knn", c_int32), ("points", c_void_p), ("index", c_void_p), ("radius", ctypes.c_double), ("orient", c_int32),
+        ("toward", ctypes.c_double * 3), ("scratch", c_void_p), ("scratch_bytes", c_size_t), ("normals", c_void_p),
+        ("covariance", c_void_p), ("neighbors", c_void_p), ("count", c_void_p), ("status", c_void_p),
+    ]
+
+
 # every symbol include/dnsplat.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "dnsplat_strerror", "dnsplat_abi_version",
@@ -365,6 +373,8 @@ EXPORTS = [
     "dnsplat_knn_points",
     # likewise: the subdivision of long triangles in front of the culling
     "dnsplat_subdivide_scratch_bytes", "dnsplat_subdivide_count", "dnsplat_subdivide_emit",
+    # likewise: the point-cloud normals (exact k-NN, covariance, smallest eigenvector)
+    "dnsplat_cloud_normals_scratch_bytes", "dnsplat_cloud_normals",
 ]
 
 _lib = None
@@ -518,6 +528,9 @@ def lib() -> ctypes.CDLL:
         L.dnsplat_subdivide_scratch_bytes.argtypes = [c_int32, c_int32]
         L.dnsplat_subdivide_count.argtypes = [ctypes.POINTER(SubdivideArgs), c_void_p]
         L.dnsplat_subdivide_emit.argtypes = [ctypes.POINTER(SubdivideArgs), c_void_p]
+        L.dnsplat_cloud_normals_scratch_bytes.restype = c_size_t
+        L.dnsplat_cloud_normals_scratch_bytes.argtypes = [c_int32, c_int32]
+        L.dnsplat_cloud_normals.argtypes = [ctypes.POINTER(CloudNormalsArgs), c_void_p]
         for name in EXPORTS:
             if name not in ("dnsplat_strerror", "dnsplat_bin_workspace_bytes", "dnsplat_bin_status_offset", "dnsplat_det_workspace_bytes",
                             "dnsplat_packed_slab_floats", "dnsplat_pose_partial_rows", "dnsplat_pearson_scratch_bytes", "dnsplat_ags_normal_scratch_bytes",
@@ -525,7 +538,8 @@ def lib() -> ctypes.CDLL:
                             "dnsplat_knn_index_bytes", "dnsplat_mc_scratch_bytes", "dnsplat_cloud_distances_scratch_bytes",
                             "dnsplat_mesh_depth_scratch_bytes", "dnsplat_mesh_cut_scratch_bytes", "dnsplat_mc_observed_scratch_bytes",
                             "dnsplat_mesh_clusters_scratch_bytes", "dnsplat_mesh_filter_scratch_bytes", "dnsplat_cloud_outlier_scratch_bytes",
-                            "dnsplat_voxel_scratch_bytes", "dnsplat_icp_scratch_bytes", "dnsplat_subdivide_scratch_bytes"):
+                            "dnsplat_voxel_scratch_bytes", "dnsplat_icp_scratch_bytes", "dnsplat_subdivide_scratch_bytes",
+                            "dnsplat_cloud_normals_scratch_bytes"):
                 getattr(L, name).restype = ctypes.c_int
         if L.dnsplat_abi_version() != ABI_VERSION:
             raise DnsplatError(f"libdnsplat ABI {L.dnsplat_abi_version()} != binding {ABI_VERSION}; rebuild")

@@ -26,7 +26,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, IcpArgs, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, SubdivideArgs, TsdfArgs, VoxelArgs, RECORD_FLOATS
+from ._lib import BackprojectArgs, BinArgs, Camera, CloudDistancesArgs, CloudNormalsArgs, CloudOutlierArgs, DensityArgs, EvalMetricsArgs, DnPost, IcpArgs, LevelPointsArgs, LevelRaysArgs, McArgs, McObservedArgs, MeshClustersArgs, MeshCutArgs, MeshDepthArgs, MeshFilterArgs, MeshSampleArgs, MeshVisibilityArgs, PoseGrads, ProjGrads, ProjOut, RasterArgs, Scene, SubdivideArgs, TsdfArgs, VoxelArgs, RECORD_FLOATS
 
 
 def _ptr(t: Optional[Tensor]):
@@ -615,6 +615,19 @@ def _subdivide_args(vertices, triangles, origin, max_edge, scratch, counts, stat
     a.cap_mid = 0 if next_vertices is None else next_vertices.shape[0] - vertices.shape[0]
     a.out_vertices, a.out_triangles, a.out_index = _ptr(out_vertices), _ptr(out_triangles), _ptr(out_index)
     a.next_vertices, a.next_triangles, a.next_origin = _ptr(next_vertices), _ptr(next_triangles), _ptr(next_origin)
+    return a
+
+
+def _cloud_normals_args(points, index, knn, radius, orient_toward, scratch, normals, status, covariance=None, neighbors=None, count=None):
+    a = CloudNormalsArgs()
+    a.N, a.knn = points.shape[0], knn
+    a.points, a.index = _ptr(points), _ptr(index)
+    a.radius = 0.0 if radius is None else radius
+    a.orient = 0 if orient_toward is None else 1
+    for k in range(3):
+        a.toward[k] = 0.0 if orient_toward is None else orient_toward[k]
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * scratch.element_size()
+    a.normals, a.covariance, a.neighbors, a.count, a.status = _ptr(normals), _ptr(covariance), _ptr(neighbors), _ptr(count), _ptr(status)
     return a
 
 

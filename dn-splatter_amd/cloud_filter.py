@@ -14,7 +14,7 @@ Both rules are stated in ``include/dnsplat.h`` and restated in ``torch_cloud_fil
 AGAINST Open3D.  Two deviations are deliberate: the voxel order is canonical (Open3D's is that of a hash map), and a voxel's mean is an
 exact fixed-point sum, within ``voxel_size * 2**-30`` of the float64 mean, so that equal inputs give equal bytes.
 
-Out of scope: ``estimate_normals``, ``remove_radius_outlier``, ``voxel_down_sample_and_trace``'s matrix form, PLY input and output.  CPU
+Out of scope: ``remove_radius_outlier``, ``voxel_down_sample_and_trace``'s matrix form, PLY input and output.  CPU
 tensors are refused; there is no CPU fallback."""
 from __future__ import annotations
 

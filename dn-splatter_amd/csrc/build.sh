@@ -30,6 +30,7 @@ $HIPCC $COMMON -ffp-contract=off -c meshclusters.hip -o _obj/meshclusters.o & pi
 $HIPCC $COMMON -ffp-contract=off -c cloudfilter.hip -o _obj/cloudfilter.o & pids+=($!)
 $HIPCC $COMMON -ffp-contract=off -c icp.hip        -o _obj/icp.o & pids+=($!)
 $HIPCC $COMMON -ffp-contract=off -c subdivide.hip  -o _obj/subdivide.o & pids+=($!)
+$HIPCC $COMMON -ffp-contract=off -c normals.hip    -o _obj/normals.o & pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC _obj/project.o _obj/binning.o _obj/raster_fwd.o _obj/raster_bwd.o _obj/c_api.o _obj/postops.o _obj/losses.o _obj/pearson.o _obj/ags.o _obj/pointcloud.o _obj/metrics.o _obj/density.o _obj/levelset.o _obj/marching.o _obj/geometry.o _obj/meshcull.o _obj/tsdf.o _obj/meshclusters.o _obj/cloudfilter.o _obj/icp.o _obj/subdivide.o -o ../libdnsplat.so
+$HIPCC --offload-arch=gfx950 -shared -fPIC _obj/project.o _obj/binning.o _obj/raster_fwd.o _obj/raster_bwd.o _obj/c_api.o _obj/postops.o _obj/losses.o _obj/pearson.o _obj/ags.o _obj/pointcloud.o _obj/metrics.o _obj/density.o _obj/levelset.o _obj/marching.o _obj/geometry.o _obj/meshcull.o _obj/tsdf.o _obj/meshclusters.o _obj/cloudfilter.o _obj/icp.o _obj/subdivide.o _obj/normals.o -o ../libdnsplat.so
 echo "built $(realpath ../libdnsplat.so)"

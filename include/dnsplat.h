@@ -76,6 +76,7 @@ extern "C" {
  * dnsplat_transform_points / dnsplat_knn_points: the mesh alignment (point-to-point ICP) in front of the culling;
  * dnsplat_subdivide_scratch_bytes / dnsplat_subdivide_count / dnsplat_subdivide_emit / dnsplat_subdivide_args: the subdivision of
  * long triangles the culling starts with;
+ * dnsplat_cloud_normals_scratch_bytes / dnsplat_cloud_normals / dnsplat_cloud_normals_args: the point-cloud normals (exact k-NN PCA);
  * dnsplat_bin_prepare_cells / dnsplat_bin_emit_sort_cells / dnsplat_bin_cells / dnsplat_raster_fwd_cells / dnsplat_raster_bwd_cells /
  * dnsplat_raster_cells / dnsplat_det_reduce_planes: the fused path's tile lists kept per cell of several tiles). */
 #define DNSPLAT_ABI_VERSION 15
@@ -1348,7 +1349,7 @@ int dnsplat_mesh_filter_emit(const dnsplat_mesh_filter_args *args, dnsplat_strea
  * Both return without touching the device: DNSPLAT_ERR_INVALID_ARG for a NULL args or required pointer, N < 1, voxel_size not in
  * (0, inf), a negative cap_v or a positive one without the buffer of an array that was given; DNSPLAT_ERR_UNSUPPORTED for
  * N > (2^31 - 1) / 2; DNSPLAT_ERR_WORKSPACE for a short or misaligned scratch.
- * Out of scope: estimate_normals, remove_radius_outlier, voxel_down_sample_and_trace's matrix form, PLY input and output. */
+ * Out of scope: remove_radius_outlier, voxel_down_sample_and_trace's matrix form, PLY input and output. */
 #define DNSPLAT_CLOUD_OUTLIER_STATS_BYTES 64
 #define DNSPLAT_VOXEL_STATUS_INTERNAL 1
 #define DNSPLAT_VOXEL_STATUS_NONFINITE 2
@@ -1563,6 +1564,80 @@ typedef struct dnsplat_subdivide_args {
 size_t dnsplat_subdivide_scratch_bytes(int32_t V, int32_t T);   /* 0 for an invalid size */
 int dnsplat_subdivide_count(const dnsplat_subdivide_args *args, dnsplat_stream_t stream);
 int dnsplat_subdivide_emit(const dnsplat_subdivide_args *args, dnsplat_stream_t stream);
+
+/* ------------------------------------------------------------------ point-cloud normals (added after ABI 15, found by symbol)
+ * Open3D's PointCloud.estimate_normals, which the reference calls in two places: the seed normals of its dataparsers
+ * (_load_points3D_normals in normal_nerfstudio.py:85-101, replica_dataparser.py:381, nrgbd_dataparser.py:378,
+ * scannetpp_dataparser.py:593, mushroom_dataparser.py:758, coolermap_dataparser.py:334, g_sdfstudio_dataparser.py:270:
+ * KDTreeSearchParamHybrid(radius = 0.1, max_nn = 30), from which dn_model.py:196-215 initialises the Gaussians' normals), and the normals
+ * of a sensor depth frame (scripts/depth_to_normal.py:150-213, scripts/depth_normal_consistency.py:171-221: KDTreeSearchParamKNN(200)
+ * over every pixel).  Open3D is not at hand: the rule is restated from memory of PointCloud::EstimateNormals and
+ * OrientNormalsTowardsCameraLocation, IT IS THIS PROJECT'S DEFINITION, PARITY UNPINNED AGAINST Open3D.  torch_normals.py restates it on
+ * the CPU.  Everything is caller-allocated; nothing is read on the host, allocated or synchronised; no floating-point atomic, every
+ * loop bounded by the sizes: equal inputs give equal bytes.
+ *
+ * For point i of points fp32 [N,3], with `index` = dnsplat_knn_build over the SAME points:
+ *   neighbours K = min(knn, N).  The K points with the smallest key (d2, index) under dnsplat_knn_query's d2 — coordinates widened to
+ *              double, d2 = fma(dz, dz, fma(dy, dy, dx dx)) — the point itself included; equal d2 go to the lowest index, so the set is
+ *              canonical.  With a radius (Open3D's hybrid search) of those K the ones with d2 < radius radius are kept, the product in
+ *              double: a strict test, as Open3D takes a lower bound on the sorted squared distances.  n = the number kept.  A row
+ *              with a non-finite coordinate has n = 0 and is nobody's neighbour.
+ *   moments    in double, over the kept neighbours in ascending (d2, index) rank t = 0 .. n - 1, by ONE FIXED TREE: the partial of
+ *              lane l = t mod 64 adds its terms t = l, l + 64, l + 128, l + 192 in this order from 0; the 64 partials are then
+ *              added pairwise, v[l] = v[l] + v[l xor o] for o = 32, 16, 8, 4, 2, 1.  The mean m = (sum of p_j) / n; then the six sums
+ *              of (p_j - m)(p_j - m)^T in the order xx, xy, xz, yy, yz, zz by the same tree, C = sum / n.  Two passes about the mean,
+ *              NOT Open3D's cumulants: a deliberate deviation, better conditioned at no cost here.  No contraction to a fused
+ *              multiply-add.  n = 0: C = 0.
+ *   normal     the unit eigenvector of the smallest eigenvalue of C: 8 cyclic Jacobi sweeps in double over the planes (0,1), (0,2),
+ *              (1,2), the rotation of dnsplat_icp's solve (theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| +
+ *              sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c); an a_pq that is zero, or that changes neither |a_pp| nor |a_qq|
+ *              when its magnitude is added to them, is set to zero without a rotation.  The column of the smallest diagonal entry,
+ *              equal ones to the lowest column, divided once by sqrt((e0 e0 + e1 e1) + e2 e2).  n < 3, or a C whose six entries are
+ *              all zero: (0, 0, 1), Open3D's fallback.
+ *   sign       without orient: canonical — the component of largest magnitude is positive, the lowest axis on equal magnitudes
+ *              (Open3D leaves the sign arbitrary).  With orient (orient_normals_towards_camera_location(toward)): the normal is
+ *              negated iff (n0 (c0 - p0) + n1 (c1 - p1)) + n2 (c2 - p2) < 0 in double, p the point widened; a product of exactly 0
+ *              does not flip.  The fallback is oriented like any other normal.
+ * dnsplat_cloud_normals — ONE launch, one wave of 64 lanes per point: the cube rings of dnsplat_knn_query's search read row by row
+ *   as coalesced runs of the index, the candidates below the threshold appended to a buffer of 2 KP entries in the wave's LDS (KP = knn
+ *   rounded up to a power of two, at least 64), a bitonic sort of that buffer keeping the K lowest whenever a batch of 64 would not fit
+ *   and at the end of each ring that left K or more; the search ends as dnsplat_knn_query's does (the K-th d2 below the bound of what
+ *   lies outside the cube, with the same 1 -+ 4e-7 factors), or when that bound is not below radius radius.  Outputs: normals double
+ *   [N,3]; optional (NULL to skip, the normals are the same bytes either way) covariance double [N,6], neighbors int32 [N,knn]
+ *   ascending by (d2, index) with -1 past n, count int32 [N] = n.
+ * status: device int32 [1], zeroed by the CALLER; it stays 0 on a correct build: DNSPLAT_NORMALS_STATUS_INTERNAL — the rings ran out
+ *   before the cube covered the grid (cannot happen).
+ * scratch: dnsplat_cloud_normals_scratch_bytes(N, knn) = 16 bytes, 8-byte aligned, zeroed by the CALLER: int32 [4] = {the widest ring a
+ *   query reached, the most selections one query ran, 0, 0}, two integer maxima for tests and timing; 0 for N < 1 or knn outside
+ *   [3, DNSPLAT_NORMALS_MAX_K].
+ * Returns before anything touches a device: DNSPLAT_ERR_INVALID_ARG for a NULL args or required pointer, N < 1, a nan radius (radius <= 0
+ *   or +inf: no radius), orient outside {0, 1}, a nan in toward with orient; DNSPLAT_ERR_UNSUPPORTED for knn outside
+ *   [3, DNSPLAT_NORMALS_MAX_K]; DNSPLAT_ERR_WORKSPACE for a short or misaligned scratch.
+ * Known limit: a far, isolated point widens its cube ring by ring until the K-th neighbour is certain (or, with a radius, only until the
+ *   bound passes it).  Infinite coordinates are not supported by the index (its box loses its extent); nan rows are.
+ * Out of scope: a pure radius search with unbounded count, orient_normals_consistent_tangent_plane, covariance-weighted or
+ * fast-approximate normals, Poisson reconstruction, PLY input and output, a k-NN index for thin shells, widening dnsplat_knn_query
+ * beyond DNSPLAT_KNN_MAX_K. */
+#define DNSPLAT_NORMALS_MAX_K 256
+#define DNSPLAT_NORMALS_STATUS_INTERNAL 1
+typedef struct dnsplat_cloud_normals_args {
+    int32_t N;
+    int32_t knn;                /* Open3D's knn / max_nn: 3 .. DNSPLAT_NORMALS_MAX_K */
+    const float *points;        /* [N,3] */
+    const void *index;          /* dnsplat_knn_build's, over the same points */
+    double radius;              /* the hybrid search's radius; <= 0 or +inf: none */
+    int32_t orient;             /* 1: towards `toward`; 0: the canonical sign */
+    double toward[3];
+    void *scratch;
+    size_t scratch_bytes;
+    double *normals;            /* [N,3] */
+    double *covariance;         /* [N,6] xx, xy, xz, yy, yz, zz, or NULL */
+    int32_t *neighbors;         /* [N,knn], or NULL */
+    int32_t *count;             /* [N], or NULL */
+    int32_t *status;            /* device int32 [1]; the caller zeroes it */
+} dnsplat_cloud_normals_args;
+size_t dnsplat_cloud_normals_scratch_bytes(int32_t N, int32_t knn);   /* 0 for an invalid size */
+int dnsplat_cloud_normals(const dnsplat_cloud_normals_args *args, dnsplat_stream_t stream);
 
 /* The per-Gaussian term of the same loss (regularization_strategy.py:195-199): mean_g min_k exp(scales[g][k]).  Adds
  * weight * sum_g min_k exp(s_gk) to *sum (device scalar, caller zeroes it) and WRITES the gradient rows
